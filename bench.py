@@ -9,10 +9,18 @@ GPU at C2. Synthetic data and hash-PRNG weights of the real architecture (checkp
 network-only); inputs are resident on the device before the timed region.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2|c3|c4|c5] [--compute bf16|fp16]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, weak scaling)
 
 `--gpus N` alone starts the N rank processes itself (one per GPU, RCCL); under an outer launcher
 (torchrun) WORLD_SIZE must equal N. Prints ONE JSON line on rank 0 (contract in the task statement).
+
+A plain run does only what the headline figure needs: it sets up, runs W warm-up steps, times exactly K
+steps (`ms_per_step` = the milliseconds one of them took), writes the last timed step's generated mels
+with `--dump-outputs DIR` (DIR/mel_<utterance>.npy, float32; the inputs, weights and noise are seeded, so
+two builds can be compared output for output) and prints the line; `roofline`, `roofline_classes`,
+`vocos` and `cpu_baseline` are then null or empty. `--full` adds those measurements, each a run of its
+own around or after the timed region (`--probe`, `--no-vocos` and `--no-cpu-baseline` trim a full run):
 `roofline` is the kernel class that takes the most time per step (in-kernel device wall-clock stamps,
 probed live over the timed region, with the committed rocprofv3 average and MFMA-busy counters of the
 class beside them); `roofline_classes` lists every class from a probe pre-pass. The default (and the
@@ -415,6 +423,14 @@ def parse_args(argv=None):
     ap.add_argument("--config", default="c2", choices=("c1", "c2", "c3", "c4", "c5"),
                     help="workload (SURVEY §8d); c2 is the headline line")
     ap.add_argument("--no-vocos", action="store_true", help="skip the +Vocos decode timing (SURVEY §8f1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-class probe pre-pass and the "
+                         "live roofline probe (--probe), the +Vocos decode and the CPU baseline. Without it the run "
+                         "sets up, warms up, times the steps and prints the line; those fields are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last timed step's generated mels to DIR/mel_<utterance>.npy "
+                         "(float32 [generated frames, channels]); at most 64 MB, a seeded sample of the utterances "
+                         "beyond that")
     # launcher test hook: the rank processes run the job driver on CPU over gloo with a stand-in sampler
     ap.add_argument("--standin", action="store_true", help=argparse.SUPPRESS)
     return ap.parse_args(argv)
@@ -515,6 +531,9 @@ def main(argv=None):
     if args.gpus < 1:
         print("bench.py: --gpus must be >= 1", file=sys.stderr)
         return 2
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
+        return 2
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is not None:
         if int(env_world) != args.gpus:
@@ -559,6 +578,34 @@ def _time_region(step, steps, world, device):
     return elapsed, joined
 
 
+DUMP_CAP_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, mels, cap=DUMP_CAP_BYTES):
+    """Write what one step returned ({utterance index: generated mel [frames, C]}, the value of
+    parallel.run_sharded) as path/mel_<index>.npy in float32. A job larger than `cap` bytes is cut to a
+    fixed sample of its utterances (a seeded shuffle of the indices, taken while they fit), the same in
+    every run. Returns the indices written."""
+    import random
+
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    keys = sorted(mels)
+    if sum(mels[k].numel() * 4 for k in keys) > cap:
+        order = list(keys)
+        random.Random(0).shuffle(order)
+        keys, used = [], 0
+        for k in order:
+            if used + mels[k].numel() * 4 <= cap:
+                keys.append(k)
+                used += mels[k].numel() * 4
+        keys.sort()
+    for k in keys:
+        np.save(os.path.join(path, f"mel_{k:05d}.npy"), mels[k].detach().float().cpu().numpy())
+    return keys
+
+
 def run_standin(args):
     """Launcher test (CPU): every rank runs parallel.run_sharded over gloo with a deterministic stand-in
     sampler on a small job, through the same timed region and line as the real bench."""
@@ -580,12 +627,17 @@ def run_standin(args):
 
     plan_all = parallel.plan([u["total"] for u in utts], world, max_batch=4)
 
+    last = {}
+
     def step():
-        return parallel.run_sharded(utts, sample, rank=rank, world=world, device=device, plan_all=plan_all)
+        last["mels"] = parallel.run_sharded(utts, sample, rank=rank, world=world, device=device, plan_all=plan_all)
+        return last["mels"]
 
     for _ in range(args.warmup):
         got = step()
     elapsed, joined = _time_region(step, args.steps, world, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["mels"])
     frames = sum(u["total"] - u["ref"] for u in utts) * args.steps
     got = step()  # a collective: every rank takes part
     if rank == 0:
@@ -636,8 +688,11 @@ def run_rank(args):
                               keep_trajectory=False)
         return out
 
+    last = {}  # what the newest step returned (--dump-outputs writes the last timed step's)
+
     def step():
-        return parallel.run_sharded(utts, sample, rank=rank, world=world, device=device, plan_all=plan_all)
+        last["mels"] = parallel.run_sharded(utts, sample, rank=rank, world=world, device=device, plan_all=plan_all)
+        return last["mels"]
 
     eng = model.transformer.get_engine(model.engine_compute(), device)
     esz = 4 if args.compute == "fp32" else 2
@@ -659,24 +714,25 @@ def run_rank(args):
         step()
     torch.cuda.synchronize()
 
-    # ---- probe pre-pass: every kernel class timed by its in-kernel stamps, one call each (skipped with
-    # --probe none: plain timing runs, e.g. interleaved A/B)
-    t0 = time.perf_counter()
-    step()
-    torch.cuda.synchronize()
-    ms_pre = (time.perf_counter() - t0) * 1e3
+    # ---- probe pre-pass (--full): every kernel class timed by its in-kernel stamps, one call each (skipped
+    # with --probe none: plain timing runs, e.g. interleaved A/B). Without --full nothing is probed.
+    probe = args.probe if args.full else "none"
     classes = {}
-    for kc in (PROBE_CLASSES if args.probe != "none" else ()):
-        eng.probe(kc)
-        step()  # captures the probed step graph (the probe is part of the graph key)
+    if probe != "none":
+        t0 = time.perf_counter()
         step()
         torch.cuda.synchronize()
-        n, ms = eng.probe_read()
-        eng.probe(None)
-        if n:
-            classes[kc] = class_entry(kc, ms / n, n, arch, S, L, launches[kc] * case["nfe"], ms_pre, chains,
-                                      config=args.config, esz=esz, compute=args.compute, qlens=qlens)
-    probe = args.probe
+        ms_pre = (time.perf_counter() - t0) * 1e3
+        for kc in PROBE_CLASSES:
+            eng.probe(kc)
+            step()  # captures the probed step graph (the probe is part of the graph key)
+            step()
+            torch.cuda.synchronize()
+            n, ms = eng.probe_read()
+            eng.probe(None)
+            if n:
+                classes[kc] = class_entry(kc, ms / n, n, arch, S, L, launches[kc] * case["nfe"], ms_pre, chains,
+                                          config=args.config, esz=esz, compute=args.compute, qlens=qlens)
     if probe == "auto":
         probe = max(classes, key=lambda k: classes[k]["share_of_call"] or 0.0) if classes else "none"
 
@@ -685,6 +741,8 @@ def run_rank(args):
         eng.probe(probe)
         step()
     elapsed, joined = _time_region(step, args.steps, world, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["mels"])
     roof = None
     if probe != "none":
         n_launch, probe_ms = eng.probe_read()
@@ -706,7 +764,7 @@ def run_rank(args):
     # generated mel after sampling (utils_infer.py:506-511, benchmark.py:430-435); timed separately
     # on the same device, K rounds over this rank's utterances, bf16 backbone + fp32 iSTFT head.
     vocos = None
-    if not args.no_vocos:
+    if args.full and not args.no_vocos:
         from f5_tts_amd.vocos import Vocos, make_weights as vocos_weights
 
         voc = Vocos(compute="bf16")
@@ -738,7 +796,7 @@ def run_rank(args):
                          "synthetic weights; rtf_with_vocos = (CFM + Vocos wall) / generated audio seconds"}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         hc = host_cores()
         cpu = cpu_baseline(args.config, case, arch, threads=hc["usable"])
         cpu["host_cores"] = hc
@@ -776,6 +834,7 @@ def run_rank(args):
             "config": {"workload": workloads[args.config], "batch_per_gpu": B, "frames": Nmax,
                        "gen_frames_per_gpu": gen_frames, "nfe": case["nfe"], "parallelism": f"dp{world}"},
             "ranks_joined": joined,
+            "full": args.full,
             "rtf": round(rtf, 5),
             "path_tflops": round(flops_call * args.steps * world / elapsed / 1e12, 2),
             "path_tflops_useful": round(useful_call * args.steps * world / elapsed / 1e12, 2),

@@ -173,18 +173,54 @@ def _bench_cmd(*args, env=None):
                           env=e)
 
 
-def test_gpus_n_starts_n_ranks_and_prints_one_line():
+def test_gpus_n_starts_n_ranks_and_prints_one_line(tmp_path):
     """`bench.py --gpus 2` with no outer launcher starts 2 rank processes itself (gloo stand-in worker on
-    CPU): both ranks join the timed region, rank 0 prints exactly one JSON line with n_gpus 2, dp2."""
+    CPU): both ranks join the timed region, rank 0 prints exactly one JSON line with n_gpus 2, dp2, and
+    `--dump-outputs` writes the gathered mels of the last timed step (the stand-in's mel of utterance i is
+    its total length 64 + 8 i over total - ref frames)."""
     import json
 
-    r = _bench_cmd("--gpus", "2", "--standin", "--steps", "2", "--warmup", "1")
+    import numpy as np
+
+    r = _bench_cmd("--gpus", "2", "--standin", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "o"))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["ranks_joined"] == 2 and d["config"]["parallelism"] == "dp2"
-    assert d["utterances_gathered"] == 8 and d["steps"] == 2
+    assert d["utterances_gathered"] == 8 and d["steps"] == 2 and d["ms_per_step"] > 0
+    assert sorted(p.name for p in (tmp_path / "o").iterdir()) == [f"mel_{i:05d}.npy" for i in range(8)]
+    for i in range(8):
+        m = np.load(tmp_path / "o" / f"mel_{i:05d}.npy")
+        total = 64 + 8 * i
+        assert m.dtype == np.float32 and m.shape == (total - total // 2, 100) and (m == total).all()
+
+
+def test_dump_outputs_caps_with_a_fixed_sample(tmp_path):
+    """dump_outputs writes every utterance's mel as float32 while the job fits the cap; a larger job is cut
+    to a sample of utterances that is the same in every run and stays under the cap."""
+    import numpy as np
+    import torch
+
+    mels = {i: torch.full((10 + i, 4), float(i), dtype=torch.bfloat16) for i in range(6)}
+    assert bench.dump_outputs(str(tmp_path / "all"), mels) == list(range(6))
+    m = np.load(tmp_path / "all" / "mel_00003.npy")
+    assert m.dtype == np.float32 and m.shape == (13, 4) and (m == 3).all()
+    cap = 3 * 15 * 4 * 4
+    a = bench.dump_outputs(str(tmp_path / "a"), mels, cap=cap)
+    b = bench.dump_outputs(str(tmp_path / "b"), mels, cap=cap)
+    assert a == b and 0 < len(a) < 6
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == [f"mel_{i:05d}.npy" for i in a]
+    assert sum(p.stat().st_size - 128 for p in (tmp_path / "a").iterdir()) <= cap
+
+
+def test_plain_run_leaves_the_extras_to_full():
+    """`--full` is off by default; the options that trim a full run still parse without it."""
+    a = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 3
+    a = bench.parse_args(["--full", "--no-vocos", "--no-cpu-baseline", "--probe", "none", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+    assert bench.main(["--steps", "0"]) == 2
 
 
 def test_launcher_parent_makes_no_hip_call(monkeypatch, capsys):

@@ -16,7 +16,7 @@ for i in $(seq 1 ${ROUNDS:-2}); do
     for arm in ${ARMS:-base=lib_base new=lib}; do
       n=${arm%%=*}; spec=${arm#*=}; dir=${spec%%:*}; L=$LD/$dir/libf5h.so
       EV=""; [ "$spec" != "$dir" ] && EV=$(echo ${spec#*:} | tr ',' ' ')
-      env $EV F5H_LIB=$L timeout -k 10 600 python bench.py --config $c $ST --no-cpu-baseline --no-vocos --probe ${PROBE:-attention} \
+      env $EV F5H_LIB=$L timeout -k 10 600 python bench.py --full --config $c $ST --no-cpu-baseline --no-vocos --probe ${PROBE:-attention} \
         > $O/${c}_${n}_$i.log 2>&1 || { echo "$c $n $i failed"; exit 1; }
       echo "$c $n $i $(tail -1 $O/${c}_${n}_$i.log | python -c 'import sys,json; d=json.loads(sys.stdin.read()); r=d["roofline"]; print(round(d["ms_per_step"],2), r["kernel"], r.get("avg_launch_us"), r["frac"])')"
     done

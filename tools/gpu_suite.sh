@@ -15,6 +15,6 @@ if [ $rc -ne 0 ]; then
 fi
 timeout -k 10 240 python __graft_entry__.py smoke > $O/smoke.log 2>&1 && echo "smoke ok" || exit 1
 for c in ${CONFIGS:-c2 c3}; do
-  timeout -k 10 600 python bench.py --config $c --no-cpu-baseline --no-vocos ${BENCH_ARGS} > $O/bench_$c.log 2>&1 \
+  timeout -k 10 600 python bench.py --full --config $c --no-cpu-baseline --no-vocos ${BENCH_ARGS} > $O/bench_$c.log 2>&1 \
     && echo "$c $(tail -1 $O/bench_$c.log | python -c 'import sys,json; d=json.loads(sys.stdin.read()); r=d["roofline"]; print(d["ms_per_step"], d["value"], r["kernel"], r["frac"])')" || exit 1
 done
