@@ -710,6 +710,99 @@ hipError_t cfg_euler(const EulerArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------- CFG + one midpoint / rk4 evaluation
+// torchdiffeq's fixed-grid solvers, operation order as written there (fp32, uncontracted):
+//   midpoint: ymid = y0 + k1 * (0.5 dt);  y1 = y0 + dt * f(ymid)
+//   rk4 (3/8 rule), c = 1/3: y0 + dt * k1 * c;  y0 + dt * (k2 - k1 * c);  y0 + dt * (k1 - k2 + k3);
+//                            y1 = y0 + (k1 + 3 * (k2 + k3) + k4) * dt * 0.125
+// The coefficients are the tableau's (kernels.h ode_tableau); the asserts tie the written-out forms to it.
+template <typename TO, int METHOD>
+__global__ __launch_bounds__(256) void cfg_rk_kernel(RkArgs a, TO* ypad) {
+  constexpr OdeTableau T = ode_tableau(METHOD);
+  constexpr int STAGES = T.stages;
+  static_assert(METHOD == 1 || METHOD == 2, "midpoint or rk4");
+  static_assert(METHOD != 1 || (T.a[4] == T.c[1] && T.b[0] == 0.f && T.b[1] == 1.f), "midpoint tableau");
+  static_assert(METHOD != 2 || (T.a[4] == T.c[1] && T.a[8] == -T.c[1] && T.a[9] == 1.f && T.a[12] == 1.f &&
+                                T.a[13] == -1.f && T.a[14] == 1.f && T.b[1] == 3.f * T.b[0] &&
+                                T.b[2] == T.b[1] && T.b[3] == T.b[0]),
+                "3/8-rule tableau");
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t total = (int64_t)a.B * a.N * a.mel;
+  // read once, atomically: the last workgroup to arrive below bumps it (the cfg_euler protocol)
+  const int e = __hip_atomic_load(a.keval, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int k = e / STAGES, s = e - k * STAGES;
+  if (a.next_dst && e + 1 < a.neval) {  // the next evaluation's table row
+    const float4* src = reinterpret_cast<const float4*>(a.next_src + (int64_t)(e + 1) * a.next_stride);
+    float4* dst = reinterpret_cast<float4*>(a.next_dst);
+    for (int64_t j = i; j < a.next_n / 4; j += (int64_t)gridDim.x * blockDim.x) dst[j] = src[j];
+  }
+  const float dt = sub_nc(a.sgrid[k + 1], a.sgrid[k]);
+  const bool last = s == STAGES - 1;
+  float* traj = (last && a.trajp) ? *a.trajp : nullptr;
+  if (traj) traj += (int64_t)(k + 1) * total;
+  for (; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int c = (int)(i % a.mel);
+    const int64_t bn = i / a.mel;
+    const int b = (int)(bn / a.N), n = (int)(bn - (int64_t)b * a.N);
+    const float pc = a.p[(int64_t)b * a.p_seq_stride + (int64_t)(a.p_row_off + n) * a.p_ld + c];
+    float v = pc;
+    if (a.use_cfg) {
+      const float pu = a.p[(int64_t)(a.B + b) * a.p_seq_stride + (int64_t)(a.p_row_off + n) * a.p_ld + c];
+      v = add_nc(pc, mul_nc(sub_nc(pc, pu), a.cfg));
+    }
+    const float y0 = a.y[i];
+    float yn;  // the next evaluation's input: a stage point, or y1 after the final stage
+    if constexpr (METHOD == 1) {
+      yn = s == 0 ? add_nc(y0, mul_nc(v, mul_nc(T.c[1], dt))) : add_nc(y0, mul_nc(dt, v));
+    } else {
+      constexpr float c3 = T.c[1];
+      const float* K0 = a.kbuf;  // k1, k2, k3 of this step
+      const float* K1 = K0 + total;
+      const float* K2 = K1 + total;
+      if (s == 0) {
+        yn = add_nc(y0, mul_nc(mul_nc(dt, v), c3));
+      } else if (s == 1) {
+        yn = add_nc(y0, mul_nc(dt, sub_nc(v, mul_nc(K0[i], c3))));
+      } else if (s == 2) {
+        yn = add_nc(y0, mul_nc(dt, add_nc(sub_nc(K0[i], K1[i]), v)));
+      } else {
+        const float sum = add_nc(add_nc(K0[i], mul_nc(T.b[1] / T.b[0], add_nc(K1[i], K2[i]))), v);
+        yn = add_nc(y0, mul_nc(mul_nc(sum, dt), T.b[0]));
+      }
+      if (!last) a.kbuf[(int64_t)s * total + i] = v;
+    }
+    if (last) a.y[i] = yn;
+    ypad[bn * 128 + c] = from_f32<TO>(yn);
+    if (traj) traj[i] = yn;
+  }
+  if (a.arrive) {
+    // every thread of this workgroup has read e above: the last workgroup to arrive bumps the evaluation
+    // counter (and the probe tick) for the next evaluation's launches
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const unsigned old = __hip_atomic_fetch_add(a.arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (old == gridDim.x - 1) {
+        __hip_atomic_store(a.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(a.keval, e + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (a.tick) __hip_atomic_fetch_add(a.tick, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+}
+hipError_t cfg_rk(const RkArgs& a, hipStream_t st) {
+  if ((a.method != 1 && a.method != 2) || !a.keval || !a.sgrid || !a.ypad) return hipErrorInvalidValue;
+  if (ode_kept_slopes(a.method) > 0 && !a.kbuf) return hipErrorInvalidValue;
+  const int64_t total = (int64_t)a.B * a.N * a.mel;
+  // at most 128 workgroups, as cfg_euler: the counter bump costs one same-word atomic per workgroup
+  const unsigned blocks = std::min<unsigned>(128, std::max<unsigned>(1, nblk(total, 256)));
+  if (a.method == 1) {
+    F5H_OP_DISPATCH(a.compute, T, hipLaunchKernelGGL((cfg_rk_kernel<T, 1>), dim3(blocks), dim3(256), 0, st, a, (T*)a.ypad););
+  } else {
+    F5H_OP_DISPATCH(a.compute, T, hipLaunchKernelGGL((cfg_rk_kernel<T, 2>), dim3(blocks), dim3(256), 0, st, a, (T*)a.ypad););
+  }
+  return hipGetLastError();
+}
+
 // out = where(cond_mask, cond, out) (cfm.py:223)
 __global__ void final_where_kernel(const float* cond, const uint8_t* m, float* y, int64_t total, int mel) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

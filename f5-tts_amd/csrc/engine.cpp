@@ -72,12 +72,13 @@ struct GraphKey {
   const void* ws;
   int kind;  // 0: one NFE step, 1: the call prologue (inputs staged into the workspace)
   int B, N, nt, nfe, use_cfg, batch_mask, probe, split, pad_skip, chain, lnfold;
+  int method;  // f5h_ode_method (nfe counts evaluations = table rows: steps x stages)
   uint64_t kernel_epoch;  // bumped whenever a forced GEMM config changes
   uint32_t cfg_bits;
   bool operator==(const GraphKey& o) const {
     return ws == o.ws && kind == o.kind && B == o.B && N == o.N && nt == o.nt && nfe == o.nfe && kernel_epoch == o.kernel_epoch &&
            use_cfg == o.use_cfg && batch_mask == o.batch_mask && probe == o.probe && cfg_bits == o.cfg_bits &&
-           split == o.split && pad_skip == o.pad_skip && chain == o.chain && lnfold == o.lnfold;
+           split == o.split && pad_skip == o.pad_skip && chain == o.chain && lnfold == o.lnfold && method == o.method;
   }
 };
 
@@ -498,6 +499,8 @@ struct Bufs {
   int* kstep;                         // device-side NFE step index
   float* y;                           // ODE state [B][N][mel] fp32
   float** trajp;                      // device slot: trajectory base pointer (or null)
+  // midpoint / rk4 only: the step grid [steps + 1] (tgrid then holds the evaluation times) and the kept slopes
+  float *sgrid, *kbuf;
   // UNetT residual stream (operand dtype): xs[0..depth/2] -- layer l < depth/2 reads xs[l] (its
   // skip connection, kept) and writes xs[l+1]; later layers ping-pong between pp[0] and pp[1]
   std::vector<void*> xs;
@@ -510,7 +513,9 @@ struct Bufs {
   int32_t* in_dur;
 };
 
-static void layout(const f5h_engine* e, WS& ws, Bufs& b, int B, int N, int nfe, int use_cfg) {
+// nfe: table rows. method / steps: the multi-stage solvers' extra buffers (none for Euler, whose layout is unchanged)
+static void layout(const f5h_engine* e, WS& ws, Bufs& b, int B, int N, int nfe, int use_cfg, int method = 0,
+                   int steps = 0) {
   const f5h_arch& a = e->a;
   const int d = a.dim, td = a.text_dim, S = use_cfg ? 2 * B : B;
   const int L = a.backbone == F5H_DIT ? N : N + 1;
@@ -569,6 +574,9 @@ static void layout(const f5h_engine* e, WS& ws, Bufs& b, int B, int N, int nfe, 
     b.pp[0] = ws.take<char>(rows * d * es);
     b.pp[1] = ws.take<char>(rows * d * es);
   }
+  b.sgrid = method ? ws.take<float>((size_t)steps + 1) : nullptr;
+  const int kept = ode_kept_slopes(method);
+  b.kbuf = kept ? ws.take<float>((size_t)kept * B * N * a.mel_dim) : nullptr;
 }
 
 // ---------------------------------------------------------------- probe
@@ -606,6 +614,7 @@ struct Ctx {
   hipStream_t st;
   Bufs b;
   int B, N, nt, S, L, nfe, use_cfg, batch_mask;
+  int method, steps;  // f5h_ode_method and grid steps of an f5h_sample_ode call; nfe = steps x stages evaluations
   int drop_audio, drop_text;  // single-branch forward only (f5h_forward with cfg_infer = 0)
   hipStream_t st2;            // second stream for the unconditional branch (step-graph capture), or null
   int site;  // probe launch-site counter, reset at the start of every step's enqueue
@@ -1384,23 +1393,29 @@ void f5h_engine_destroy(f5h_engine* e) {
   });
 }
 
-size_t f5h_workspace_size(const f5h_engine* e, int32_t B, int32_t N, int32_t nt, int32_t nfe, int32_t use_cfg) {
+size_t f5h_workspace_size_ode(const f5h_engine* e, int32_t B, int32_t N, int32_t nt, int32_t steps, int32_t use_cfg,
+                             int32_t method) {
   (void)nt;
-  if (!e || B <= 0 || N <= 0 || nfe <= 0) return 0;
+  if (!e || B <= 0 || N <= 0 || steps <= 0 || method < 0 || method >= kOdeMethods) return 0;
   WS ws;
   Bufs b;
-  layout(e, ws, b, B, N, nfe + 1, use_cfg);
+  layout(e, ws, b, B, N, steps * ode_tableau(method).stages + 1, use_cfg, method, steps);
   return ws.off;
 }
+size_t f5h_workspace_size(const f5h_engine* e, int32_t B, int32_t N, int32_t nt, int32_t nfe, int32_t use_cfg) {
+  return f5h_workspace_size_ode(e, B, N, nt, nfe, use_cfg, F5H_EULER);
+}
 
-static int check_ws(f5h_engine* e, int B, int N, int nfe, int use_cfg, void* w, size_t bytes, Ctx& c) {
+// nfe: evaluations (table rows); method / steps: as layout
+static int check_ws(f5h_engine* e, int B, int N, int nfe, int use_cfg, void* w, size_t bytes, Ctx& c, int method = 0,
+                    int steps = 0) {
   WS ws;
-  layout(e, ws, c.b, B, N, nfe + 1, use_cfg);
+  layout(e, ws, c.b, B, N, nfe + 1, use_cfg, method, steps);
   if (bytes < ws.off)
     return fail(F5H_ENOMEM, "workspace too small: need " + std::to_string(ws.off) + " have " + std::to_string(bytes));
   ws.off = 0;
   ws.base = reinterpret_cast<char*>(w);
-  layout(e, ws, c.b, B, N, nfe + 1, use_cfg);
+  layout(e, ws, c.b, B, N, nfe + 1, use_cfg, method, steps);
   return 0;
 }
 
@@ -1424,6 +1439,7 @@ static GraphKey prologue_key(const Ctx& c, const void* ws) {
   key.use_cfg = c.use_cfg;
   key.batch_mask = c.batch_mask;
   key.lnfold = c.lnfold;
+  key.method = c.method;
   key.kernel_epoch = g_kernel_epoch.load();
   return key;
 }
@@ -1444,10 +1460,75 @@ static int prologue_graph(Ctx& c, const f5h_sample_args* a, const GraphKey& key)
   return note_replays(e, hold.get(), c.st);
 }
 
+// The evaluation times of the multi-stage solvers, as torchdiffeq forms them from a grid held in the parameter
+// dtype: dt = t1 - t0, then t0 + 0.5 dt (midpoint) or t0 + dt/3, t0 + dt 2/3 and t1 itself (rk4), every operation
+// on fp32 values of 16-bit operands and rounded back to the dtype (the Python scalar 1/3 enters as its fp32 value).
+// The grid arrives as fp32 values; it was built in the engine's 16-bit operand dtype (compute, f5h_compute: a model
+// run in its own precision) exactly when every value is one of that dtype's, and in fp32 otherwise (fp32
+// parameters under a 16-bit compute override), whose stage times then keep fp32 precision. out[steps * stages].
+static float round_to(int compute, float x) {
+  if (compute == F5H_FP16) return (float)(_Float16)x;
+  if (compute != F5H_BF16 || x != x) return x;
+  uint32_t u;
+  std::memcpy(&u, &x, 4);
+  u = (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u;  // round to nearest even
+  std::memcpy(&x, &u, 4);
+  return x;
+}
+static void ode_eval_times(int method, int compute, const float* t, int steps, float* out) {
+#pragma clang fp contract(off)
+  const OdeTableau T = ode_tableau(method);
+  for (int i = 0; i <= steps; ++i)
+    if (round_to(compute, t[i]) != t[i]) compute = F5H_FP32;
+  for (int k = 0; k < steps; ++k) {
+    const float t0 = t[k], t1 = t[k + 1];
+    const float dt = round_to(compute, t1 - t0);
+    for (int s = 0; s < T.stages; ++s) {
+      float v = t0;
+      if (s > 0) v = T.c[s] == 1.f ? t1 : round_to(compute, t0 + round_to(compute, dt * T.c[s]));
+      out[k * T.stages + s] = v;
+    }
+  }
+}
+
+int f5h_debug_ode_tableau(int32_t method, int32_t* stages, float* c, float* a, float* b) {
+  if (method < 0 || method >= kOdeMethods) return fail(F5H_EINVAL, "ode method must be 0 (euler), 1 (midpoint) or 2 (rk4)");
+  const OdeTableau T = ode_tableau(method);
+  if (stages) *stages = T.stages;
+  if (c) std::memcpy(c, T.c, sizeof(T.c));
+  if (a) std::memcpy(a, T.a, sizeof(T.a));
+  if (b) std::memcpy(b, T.b, sizeof(T.b));
+  return 0;
+}
+int f5h_debug_ode_eval_times(int32_t method, int32_t compute, const float* t_grid, int32_t steps, float* out) {
+  if (method < 0 || method >= kOdeMethods || compute < F5H_FP32 || compute > F5H_FP16 || !t_grid || steps <= 0 || !out)
+    return fail(F5H_EINVAL, "bad ode_eval_times argument");
+  ode_eval_times(method, compute, t_grid, steps, out);
+  return 0;
+}
+
+static int sample_impl(f5h_engine* e, void* stream, const f5h_sample_args* a, int method, void* workspace,
+                       size_t workspace_bytes);
 int f5h_sample(f5h_engine* e, void* stream, const f5h_sample_args* a, void* workspace, size_t workspace_bytes) {
+  return sample_impl(e, stream, a, F5H_EULER, workspace, workspace_bytes);
+}
+int f5h_sample_ode(f5h_engine* e, void* stream, const f5h_sample_args* a, int32_t method, void* workspace,
+                   size_t workspace_bytes) {
+  if (method < 0 || method >= kOdeMethods) return fail(F5H_EINVAL, "ode method must be 0 (euler), 1 (midpoint) or 2 (rk4)");
+  return sample_impl(e, stream, a, method, workspace, workspace_bytes);
+}
+
+// method F5H_EULER: the Euler path exactly as before the other solvers existed (same launches, same layout).
+static int sample_impl(f5h_engine* e, void* stream, const f5h_sample_args* a, int method, void* workspace,
+                       size_t workspace_bytes) {
   if (!e || !a) return fail(F5H_EINVAL, "null engine/args");
   if (a->B <= 0 || a->N <= 0 || a->nt < 0 || a->nfe <= 0 || a->nfe > 512)
     return fail(F5H_EINVAL, "bad B/N/nt/nfe");
+  const int stages = ode_tableau(method).stages;
+  if (a->nfe * stages > 512)
+    return fail(F5H_EINVAL, std::to_string(a->nfe) + " steps x " + std::to_string(stages) + " stages = " +
+                                std::to_string(a->nfe * stages) +
+                                " backbone evaluations exceed the 512 rows of the per-call time tables");
   if (!a->cond || !a->cond_mask || !a->duration || !a->y0 || !a->t_grid || !a->out || (a->nt > 0 && !a->text))
     return fail(F5H_EINVAL, "null tensor argument");
   if (e->a.backbone == F5H_DIT && a->N > 8192) return fail(F5H_EINVAL, "N exceeds the text position table (8192)");
@@ -1459,12 +1540,14 @@ int f5h_sample(f5h_engine* e, void* stream, const f5h_sample_args* a, void* work
   c.B = a->B;
   c.N = a->N;
   c.nt = a->nt;
-  c.nfe = a->nfe;
+  c.method = method;
+  c.steps = a->nfe;
+  c.nfe = a->nfe * stages;  // evaluations: the time tables hold one row each, the step graph is replayed for each
   c.use_cfg = a->cfg_strength >= 1e-5f;
   c.S = c.use_cfg ? 2 * c.B : c.B;
   c.L = e->a.backbone == F5H_DIT ? c.N : c.N + 1;
   c.batch_mask = a->use_batch_mask ? 1 : 0;
-  RC(check_ws(e, c.B, c.N, c.nfe, c.use_cfg, workspace, workspace_bytes, c));
+  RC(check_ws(e, c.B, c.N, c.nfe, c.use_cfg, workspace, workspace_bytes, c, method, c.steps));
   RC(chain_fault_check(e, c.st));
   ChainTicket ticket;  // (declared after `used`: its event is recorded first, both after every launch of the call)
   c.chain = chain_for_call(e, c, ticket);
@@ -1476,13 +1559,24 @@ int f5h_sample(f5h_engine* e, void* stream, const f5h_sample_args* a, void* work
     const char* v = getenv("F5H_PROLOGUE_GRAPH");
     return !(v && *v == '0');
   }();
-  HIPCK(grid_upload(a->t_grid, c.nfe + 1, c.b.tgrid, c.st));
-  // the ODE evaluates fn at t_0 .. t_{nfe-1}
+  // the table times: Euler evaluates fn at t_0 .. t_{nfe-1}; the multi-stage solvers at their stage times, derived
+  // here in the dtype the grid was built in (ode_eval_times), with the step grid kept beside them for dt
+  std::vector<float> evt;
+  const float* t_rows = a->t_grid;
+  if (method == F5H_EULER) {
+    HIPCK(grid_upload(a->t_grid, c.nfe + 1, c.b.tgrid, c.st));
+  } else {
+    evt.resize(c.nfe);
+    ode_eval_times(method, e->bf, a->t_grid, c.steps, evt.data());
+    t_rows = evt.data();
+    HIPCK(grid_upload(t_rows, c.nfe, c.b.tgrid, c.st));
+    HIPCK(grid_upload(a->t_grid, c.steps + 1, c.b.sgrid, c.st));
+  }
   const GraphKey pkey = prologue_key(c, workspace);
   if (pro_graph && e->graph_mode && c.nt <= c.N && prologue_repeats(e, pkey))
     RC(prologue_graph(c, a, pkey));
   else
-    RC(prologue(c, a->t_grid, c.nfe, a->cond, a->cond_mask, a->text, a->duration));
+    RC(prologue(c, t_rows, c.nfe, a->cond, a->cond_mask, a->text, a->duration));
   const double h1 = host_ms();
   const size_t ysz = (size_t)c.B * c.N * e->a.mel_dim;
   HIPCK(hipMemcpyAsync(c.b.y, a->y0, ysz * sizeof(float), hipMemcpyDeviceToDevice, c.st));
@@ -1521,6 +1615,36 @@ static int enqueue_step(Ctx& c, const f5h_sample_args* a) {
   {
     c.site = 0;
     RC(backbone_step(c));
+    const bool dit = e->a.backbone == F5H_DIT;
+    if (c.method != F5H_EULER) {  // one evaluation of a midpoint / rk4 step: same launches, cfg_rk for cfg_euler
+      RkArgs r{};
+      r.y = c.b.y;
+      r.B = c.B;
+      r.N = c.N;
+      r.mel = e->a.mel_dim;
+      r.p = c.b.p;
+      r.p_seq_stride = (int64_t)c.L * e->proj_out.Npad;
+      r.p_row_off = dit ? 0 : 1;
+      r.p_ld = e->proj_out.Npad;
+      r.use_cfg = c.use_cfg;
+      r.cfg = a->cfg_strength;
+      r.ypad = c.b.ypad;
+      r.compute = e->bf;
+      r.method = c.method;
+      r.kbuf = c.b.kbuf;
+      r.keval = c.b.kstep;
+      r.sgrid = c.b.sgrid;
+      r.trajp = c.b.trajp;
+      r.next_src = dit ? c.b.ada : c.b.temb;
+      r.next_stride = dit ? e->ada_row : e->a.dim;
+      r.next_n = dit ? (int)e->ada_row : e->a.dim;
+      r.next_dst = dit ? c.b.ada_cur : c.b.temb_cur;
+      r.neval = c.nfe;
+      r.arrive = reinterpret_cast<unsigned*>(c.b.kstep + kArrive);
+      r.tick = e->ptick;
+      KCK(cfg_rk(r, c.st));
+      return 0;
+    }
     EulerArgs u{};
     u.y = c.b.y;
     u.B = c.B;
@@ -1539,7 +1663,6 @@ static int enqueue_step(Ctx& c, const f5h_sample_args* a) {
     u.compute = e->bf;
     u.traj = nullptr;
     u.trajp = c.b.trajp;
-    const bool dit = e->a.backbone == F5H_DIT;
     u.next_src = dit ? c.b.ada : c.b.temb;
     u.next_stride = dit ? e->ada_row : e->a.dim;
     u.next_n = dit ? (int)e->ada_row : e->a.dim;
@@ -1572,6 +1695,7 @@ static int run_steps(Ctx& c, const f5h_sample_args* a, const void* ws) {
   key.pad_skip = e->pad_skip;
   key.chain = c.chain;
   key.lnfold = c.lnfold;
+  key.method = c.method;
   key.kernel_epoch = g_kernel_epoch.load();
   std::memcpy(&key.cfg_bits, &a->cfg_strength, 4);
   std::shared_ptr<GraphEntry> hold;  // keeps the replayed graph alive through the launch loop

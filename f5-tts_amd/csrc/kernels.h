@@ -193,6 +193,43 @@ struct EulerArgs {
   unsigned* arrive; int* tick;
 };
 hipError_t cfg_euler(const EulerArgs& a, hipStream_t st);
+// Fixed-grid multi-stage solvers (torchdiffeq "midpoint" and "rk4" = the 3/8 rule; f5h_ode_method numbering).
+// Butcher tableau of a method: stage times c, stage matrix a (row-major [4][4], strictly lower), weights b.
+// cfg_rk_kernel is instantiated with these values; f5h_debug_ode_tableau returns them to the CPU tests.
+constexpr int kOdeMethods = 3;
+struct OdeTableau {
+  int stages;
+  float c[4], a[16], b[4];
+};
+constexpr float kOneThird = (float)(1.0 / 3.0), kTwoThirds = (float)(2.0 / 3.0);
+constexpr OdeTableau ode_tableau(int method) {
+  return method == 1   ? OdeTableau{2, {0.f, 0.5f}, {0.f, 0.f, 0.f, 0.f, 0.5f}, {0.f, 1.f}}
+         : method == 2 ? OdeTableau{4,
+                                    {0.f, kOneThird, kTwoThirds, 1.f},
+                                    {0.f, 0.f, 0.f, 0.f, kOneThird, 0.f, 0.f, 0.f, -kOneThird, 1.f, 0.f, 0.f, 1.f, -1.f, 1.f, 0.f},
+                                    {0.125f, 0.375f, 0.375f, 0.125f}}
+                       : OdeTableau{1, {0.f}, {0.f}, {1.f}};
+}
+// Slopes a method keeps across launches: rk4's k1..k3 (read by its later stages); midpoint's k1 is used up by the
+// launch that forms it.
+constexpr int ode_kept_slopes(int method) { return method == 2 ? 3 : 0; }
+// CFG + one evaluation of a multi-stage step. The device counter *keval counts evaluations e: step k = e / stages,
+// stage s = e % stages, dt = sgrid[k+1] - sgrid[k]. A non-final stage keeps its slope in kbuf[s] (rk4) and writes
+// the next stage's input to ypad only; the final stage updates y, refreshes ypad and writes trajectory slot k+1.
+// Every evaluation copies table row e+1 (e + 1 < neval) to next_dst and the last workgroup bumps the counter, as
+// cfg_euler does. p / ypad / next_* / arrive / tick: as EulerArgs.
+struct RkArgs {
+  float* y; int B, N, mel;
+  const float* p; int64_t p_seq_stride; int p_row_off; int64_t p_ld;
+  int use_cfg; float cfg;
+  void* ypad; int compute;
+  int method;                   // 1 midpoint, 2 rk4
+  float* kbuf;                  // [ode_kept_slopes(method)][B*N*mel] fp32 (or null when none is kept)
+  int* keval; const float* sgrid; float* const* trajp;
+  const float* next_src; int64_t next_stride; int next_n; float* next_dst; int neval;
+  unsigned* arrive; int* tick;
+};
+hipError_t cfg_rk(const RkArgs& a, hipStream_t st);
 // host grid t[n <= 512] -> device (by kernel argument)
 hipError_t grid_upload(const float* t_host, int n, float* out, hipStream_t st);
 // dst[0..n) = src[k*stride ..], k = *kstep (n, stride multiples of 4)

@@ -22,6 +22,8 @@ F5H_DIT, F5H_UNETT = 0, 1
 F5H_FP32, F5H_BF16, F5H_FP16 = 0, 1, 2
 COMPUTE = {"fp32": F5H_FP32, "bf16": F5H_BF16, "fp16": F5H_FP16}
 F5H_DT_F32, F5H_DT_BF16, F5H_DT_F16 = 0, 1, 2
+F5H_EULER, F5H_MIDPOINT, F5H_RK4 = 0, 1, 2
+ODE_METHOD = {"euler": F5H_EULER, "midpoint": F5H_MIDPOINT, "rk4": F5H_RK4}
 
 # exported symbols, checked by tests/test_boundary.py against include/f5h.h
 EXPORTS = (
@@ -31,6 +33,10 @@ EXPORTS = (
     "f5h_release_pending",
     "f5h_workspace_size",
     "f5h_sample",
+    "f5h_workspace_size_ode",
+    "f5h_sample_ode",
+    "f5h_debug_ode_tableau",
+    "f5h_debug_ode_eval_times",
     "f5h_forward",
     "f5h_probe_enable",
     "f5h_probe_read",
@@ -140,6 +146,16 @@ def lib():
     L.f5h_workspace_size.restype = sz
     L.f5h_sample.argtypes = [vp, vp, ctypes.POINTER(SampleArgs), vp, sz]
     L.f5h_sample.restype = ctypes.c_int
+    if hasattr(L, "f5h_sample_ode"):  # absent from an older build loaded through F5H_LIB: Euler only (has_ode)
+        L.f5h_workspace_size_ode.argtypes = [vp, i32, i32, i32, i32, i32, i32]
+        L.f5h_workspace_size_ode.restype = sz
+        L.f5h_sample_ode.argtypes = [vp, vp, ctypes.POINTER(SampleArgs), i32, vp, sz]
+        L.f5h_sample_ode.restype = ctypes.c_int
+        fp = ctypes.POINTER(ctypes.c_float)
+        L.f5h_debug_ode_tableau.argtypes = [i32, ctypes.POINTER(i32), fp, fp, fp]
+        L.f5h_debug_ode_tableau.restype = ctypes.c_int
+        L.f5h_debug_ode_eval_times.argtypes = [i32, i32, fp, i32, fp]
+        L.f5h_debug_ode_eval_times.restype = ctypes.c_int
     L.f5h_forward.argtypes = [vp, vp, ctypes.POINTER(ForwardArgs), vp, sz]
     L.f5h_forward.restype = ctypes.c_int
     L.f5h_probe_enable.argtypes = [vp, i32, i32]
@@ -208,6 +224,11 @@ def lib():
     L.f5h_version.restype = ctypes.c_char_p
     _lib = L
     return L
+
+
+def has_ode() -> bool:
+    """False for an older build (F5H_LIB) without f5h_sample_ode: such a library samples with Euler only."""
+    return hasattr(lib(), "f5h_sample_ode")
 
 
 def check(rc: int, what: str = "f5h"):

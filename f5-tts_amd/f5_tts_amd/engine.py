@@ -38,6 +38,14 @@ def _arch_struct(arch: dict, compute: str) -> _lib.Arch:
     return a
 
 
+def _ode_method(method: str) -> int:
+    if method not in _lib.ODE_METHOD:
+        raise NotImplementedError(f"ode method {method!r}: the engine has 'euler', 'midpoint' and 'rk4'")
+    if method != "euler" and not _lib.has_ode():
+        raise RuntimeError(f"the loaded libf5h.so has no f5h_sample_ode (an older build): ode method {method!r} needs it")
+    return _lib.ODE_METHOD[method]
+
+
 class Engine:
     """One packed model on one device. Immutable after construction, so one instance may
     serve concurrent `sample` calls from several host threads (each call allocates its own
@@ -96,8 +104,12 @@ class Engine:
             self._h = None
 
     # ------------------------------------------------------------------ workspace
-    def workspace_bytes(self, B, N, nt, nfe, use_cfg=True) -> int:
-        return int(_lib.lib().f5h_workspace_size(self._h, B, N, nt, nfe, int(use_cfg)))
+    def workspace_bytes(self, B, N, nt, nfe, use_cfg=True, method="euler") -> int:
+        """Bytes for a call of `nfe` grid steps with the solver `method` ("euler", "midpoint", "rk4")."""
+        m = _ode_method(method)
+        if not _lib.has_ode():
+            return int(_lib.lib().f5h_workspace_size(self._h, B, N, nt, nfe, int(use_cfg)))
+        return int(_lib.lib().f5h_workspace_size_ode(self._h, B, N, nt, nfe, int(use_cfg), m))
 
     def _workspace(self, nbytes):
         return torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
@@ -167,10 +179,12 @@ class Engine:
 
     # ------------------------------------------------------------------ calls
     def sample(self, cond, cond_mask, text, duration, y0, t_grid, cfg_strength, use_batch_mask,
-               out=None, keep_trajectory=True, workspace=None):
+               out=None, keep_trajectory=True, workspace=None, method="euler"):
         """Run the CFM ODE loop. Tensors on this engine's device:
         cond f32 [B,N,mel], cond_mask bool/u8 [B,N], text int64 [B,nt], duration int [B],
-        y0 f32 [B,N,mel]; t_grid: host sequence of nfe+1 floats."""
+        y0 f32 [B,N,mel]; t_grid: host sequence of nfe+1 floats, the step grid. method: the fixed-grid
+        solver, "euler", "midpoint" or "rk4" (1, 2, 4 backbone evaluations per step; f5h_sample_ode);
+        the trajectory holds the nfe+1 grid points for every method."""
         B, N, mel = cond.shape
         nt = text.shape[1]
         tg = np.ascontiguousarray(np.asarray(t_grid, dtype=np.float32))
@@ -185,7 +199,8 @@ class Engine:
         traj = (torch.empty(nfe + 1, B, N, mel, dtype=torch.float32, device=self.device)
                 if keep_trajectory else None)
         use_cfg = cfg_strength >= 1e-5
-        need = self.workspace_bytes(B, N, nt, nfe, use_cfg)
+        m = _ode_method(method)
+        need = self.workspace_bytes(B, N, nt, nfe, use_cfg, method)
         stream = _lib.stream_handle(self.device)
         if workspace is not None and workspace.numel() >= need:
             ws, wlock = workspace, threading.Lock()
@@ -201,8 +216,12 @@ class Engine:
         a.out = out.data_ptr()
         a.trajectory = traj.data_ptr() if traj is not None else None
         with torch.cuda.device(self.device), wlock:
-            _lib.check(_lib.lib().f5h_sample(self._h, stream, ctypes.byref(a), ws.data_ptr(), ws.numel()),
-                       "f5h_sample")
+            if _lib.has_ode():
+                _lib.check(_lib.lib().f5h_sample_ode(self._h, stream, ctypes.byref(a), m, ws.data_ptr(), ws.numel()),
+                           "f5h_sample_ode")
+            else:  # an older build through F5H_LIB (one-box A/Bs): its Euler entry
+                _lib.check(_lib.lib().f5h_sample(self._h, stream, ctypes.byref(a), ws.data_ptr(), ws.numel()),
+                           "f5h_sample")
         return out, traj
 
     def forward_workspace(self, B, N, nt, cfg_infer=True):

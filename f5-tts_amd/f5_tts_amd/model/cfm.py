@@ -4,8 +4,9 @@
 `CFM.sample` keeps the reference signature and return tuple (`cfm.py:83-102,229`). The host
 preamble (mel intake, tokenisation, duration rule, cond padding/masks, noise recipe, time
 grid) is restated here in PyTorch exactly as `cfm.py:105-216` does it; the ODE loop, the
-backbone forwards, CFG, the Euler update and the final cond overwrite run in the HIP
-engine (`f5h_sample`, include/f5h.h). There is no PyTorch fallback for the loop.
+backbone forwards, CFG, the solver update (fixed-grid Euler, midpoint or rk4, chosen by
+`odeint_kwargs["method"]` as in the reference) and the final cond overwrite run in the HIP
+engine (`f5h_sample_ode`, include/f5h.h). There is no PyTorch fallback for the loop.
 """
 
 from __future__ import annotations
@@ -17,7 +18,7 @@ import torch.nn.functional as F
 from torch import nn
 from torch.nn.utils.rnn import pad_sequence
 
-from .utils import default, exists, lens_to_mask, list_str_to_idx, list_str_to_tensor, time_grid
+from .utils import ODE_STAGES, default, exists, lens_to_mask, list_str_to_idx, list_str_to_tensor, time_grid
 
 
 def _host_ints(x, batch):
@@ -63,9 +64,14 @@ class CFM(nn.Module):
                  mel_spec_kwargs: dict = dict(), frac_lengths_mask=(0.7, 1.0), vocab_char_map: dict | None = None,
                  compute: str = "auto"):
         super().__init__()
-        if odeint_kwargs.get("method", "euler") != "euler":
-            raise NotImplementedError("the engine integrates with fixed-grid Euler (the reference default, "
-                                      "utils_infer.py:62 ode_method='euler')")
+        method = odeint_kwargs.get("method", "euler")
+        if method not in ODE_STAGES:
+            raise NotImplementedError(f"ode method {method!r}: the engine integrates on the fixed grid with 'euler' "
+                                      "(the reference default, utils_infer.py:62), 'midpoint' or 'rk4'")
+        if "options" in odeint_kwargs:
+            raise NotImplementedError("odeint options (such as step_size) would change the grid; the engine "
+                                      "integrates 'euler', 'midpoint' or 'rk4' on the grid of cfm.py:211-216")
+        self.ode_method = method
         self.frac_lengths_mask = frac_lengths_mask
         if mel_spec_module is None:
             from ..mel import MelSpec
@@ -179,7 +185,7 @@ class CFM(nn.Module):
 
         eng = self.transformer.get_engine(self.engine_compute(), self.device)
         out, traj = eng.sample(cond.float(), cond_mask, text, duration, y0.float(), t_host, float(cfg_strength),
-                               use_batch_mask, keep_trajectory=keep_trajectory)
+                               use_batch_mask, keep_trajectory=keep_trajectory, method=self.ode_method)
         out = out.to(pdtype)
         if traj is not None:
             traj = traj.to(pdtype)

@@ -64,6 +64,26 @@ def time_grid(steps: int, sway_sampling_coef, use_epss: bool, device, dtype, t_s
     return t
 
 
+ODE_STAGES = {"euler": 1, "midpoint": 2, "rk4": 4}
+
+
+def ode_eval_times(t: torch.Tensor, method: str) -> torch.Tensor:
+    """The times at which torchdiffeq's fixed-grid solver `method` evaluates the flow on the grid `t`
+    ([steps+1]), step by step, in t's dtype: [steps * stages]. euler: t0; midpoint: t0, t0 + 0.5 dt;
+    rk4 (the 3/8 rule): t0, t0 + dt/3, t0 + dt 2/3 and the grid value t1 itself; dt = t1 - t0."""
+    if method not in ODE_STAGES:
+        raise NotImplementedError(f"ode method {method!r}: the engine has 'euler', 'midpoint' and 'rk4'")
+    t0, t1 = t[:-1], t[1:]
+    dt = t1 - t0
+    if method == "euler":
+        cols = [t0]
+    elif method == "midpoint":
+        cols = [t0, t0 + 0.5 * dt]
+    else:
+        cols = [t0, t0 + dt * (1 / 3), t0 + dt * (2 / 3), t1]
+    return torch.stack(cols, dim=1).reshape(-1)
+
+
 def get_tokenizer(vocab_path: str):
     """vocab.txt (one token per line) -> ({token: idx}, size) like tokenizer='custom' (utils.py:112-142)."""
     with open(vocab_path, "r", encoding="utf-8") as f:

@@ -142,6 +142,34 @@ size_t f5h_workspace_size(const f5h_engine* eng, int32_t B, int32_t N, int32_t n
 int f5h_sample(f5h_engine* eng, void* stream, const f5h_sample_args* args, void* workspace,
                size_t workspace_bytes);
 
+/* Fixed-grid ODE solvers of the sampler (cfm.py:218 hands odeint_kwargs["method"] to torchdiffeq; the reference's
+ * E2-TTS evaluation runs "midpoint"). Per grid interval [t0, t1], dt = t1 - t0, f = the CFG-combined flow:
+ *   F5H_EULER:    y1 = y0 + dt f(t0, y0)
+ *   F5H_MIDPOINT: h = 0.5 dt; y1 = y0 + dt f(t0 + h, y0 + k1 h), k1 = f(t0, y0)
+ *   F5H_RK4:      torchdiffeq's "rk4", the 3/8 rule, c = 1/3: k1 = f(t0, y0), k2 = f(t0 + dt c, y0 + dt k1 c),
+ *                 k3 = f(t0 + dt 2/3, y0 + dt (k2 - k1 c)), k4 = f(t1, y0 + dt (k1 - k2 + k3)),
+ *                 y1 = y0 + (k1 + 3 (k2 + k3) + k4) dt 0.125
+ * 1, 2 and 4 backbone evaluations per step. */
+enum f5h_ode_method { F5H_EULER = 0, F5H_MIDPOINT = 1, F5H_RK4 = 2 };
+
+/* f5h_workspace_size / f5h_sample with the solver chosen (F5H_EULER: the same bytes, and bitwise f5h_sample).
+ * args->nfe counts grid STEPS and args->t_grid is the step grid [nfe+1]; the trajectory keeps torchdiffeq's
+ * meaning, grid points only: [nfe+1,B,N,mel]. The engine derives the stage times from the grid on the host, in
+ * the dtype the grid was built in, as the reference does with its parameter-dtype grid: the engine's 16-bit
+ * operand dtype (f5h_arch.compute) when every grid value is one of that dtype's (dt and the stage times are then
+ * rounded to it), fp32 otherwise. It runs nfe x stages evaluations: one table row and one replay of the captured
+ * evaluation graph each, the graph keyed by the method as well. nfe x stages may not exceed 512 (F5H_EINVAL). */
+size_t f5h_workspace_size_ode(const f5h_engine* eng, int32_t B, int32_t N, int32_t nt, int32_t steps,
+                              int32_t use_cfg, int32_t method);
+int f5h_sample_ode(f5h_engine* eng, void* stream, const f5h_sample_args* args, int32_t method, void* workspace,
+                   size_t workspace_bytes);
+/* Test hooks (host only, no device needed). f5h_debug_ode_tableau: the Butcher tableau the solver kernel is
+ * instantiated with: *stages, stage times c[4], stage matrix a[16] (row-major 4x4, strictly lower), weights b[4];
+ * entries past the method's stages are 0. f5h_debug_ode_eval_times: the steps x stages evaluation times the engine
+ * derives from the step grid t_grid[steps+1] for an engine of operand dtype `compute` (f5h_compute). */
+int f5h_debug_ode_tableau(int32_t method, int32_t* stages, float* c, float* a, float* b);
+int f5h_debug_ode_eval_times(int32_t method, int32_t compute, const float* t_grid, int32_t steps, float* out);
+
 /* One backbone forward: the backbone plugin contract DiT.forward / UNetT.forward
  * (dit.py:319-370, unett.py:244-307) with a scalar time t.
  *   cfg_infer = 1: the packed cond/uncond forward CFM.sample uses (cfm.py:181-191): pred [2B,N,mel],
