@@ -330,6 +330,33 @@ static int vec_upload(f5h_engine* e, const WMap& W, const std::string& n, int64_
   return 0;
 }
 
+// ConvPositionEmbedding weight [d, d/16, 31] (element type src_dt) -> the conv kernels' panel [16][31][64 out][64 in]
+// (element type dst_dt): dst (g, t, o, i) <- src ((g*cg + o)*cg + i)*31 + t, cg = d / 16. dst holds kConvPackElems
+// elements and is zero on entry (groups narrower than 64 channels keep zero padding). Engine creation and
+// f5h_op_conv_pos both pack through here.
+static constexpr size_t kConvPackElems = (size_t)16 * 31 * 64 * 64;
+static int pack_conv_weight(const void* src, int src_dt, int d, void* dst, int dst_dt, hipStream_t st) {
+  const int cg = d / 16;
+  PackArgs pa{};
+  pa.src = src;
+  pa.src_dt = src_dt;
+  pa.src_st[0] = (int64_t)cg * cg * 31;  // g
+  pa.src_st[1] = 1;                      // t
+  pa.src_st[2] = (int64_t)cg * 31;       // o
+  pa.src_st[3] = 31;                     // i
+  pa.dst = dst;
+  pa.dst_dt = dst_dt;
+  pa.dst_st[0] = 31 * 64 * 64;
+  pa.dst_st[1] = 64 * 64;
+  pa.dst_st[2] = 64;
+  pa.n[0] = 16;
+  pa.n[1] = 31;
+  pa.n[2] = cg;
+  pa.n[3] = cg;
+  HIPCK(pack_strided(pa, st));
+  return 0;
+}
+
 static int pack_all(f5h_engine* e, const WMap& W) {
   const f5h_arch& a = e->a;
   const int d = a.dim, inner = a.heads * a.dim_head, F = a.ff_dim, td = a.text_dim, mel = a.mel_dim;
@@ -394,24 +421,8 @@ static int pack_all(f5h_engine* e, const WMap& W) {
     const int cg = d / 16;
     const WView* w = W.get(p + "weight", (int64_t)d * cg * 31, &err);
     if (!w) return fail(F5H_ENOWEIGHT, err);
-    RC(dalloc(e, (size_t)16 * 31 * 64 * 64 * e->esz, &e->conv_w[j]));
-    PackArgs pa{};
-    pa.src = w->p;
-    pa.src_dt = w->dt;
-    pa.src_st[0] = (int64_t)cg * cg * 31;  // g
-    pa.src_st[1] = 1;                      // t
-    pa.src_st[2] = (int64_t)cg * 31;       // o
-    pa.src_st[3] = 31;                     // i
-    pa.dst = e->conv_w[j];
-    pa.dst_dt = op_dt(e);
-    pa.dst_st[0] = 31 * 64 * 64;
-    pa.dst_st[1] = 64 * 64;
-    pa.dst_st[2] = 64;
-    pa.n[0] = 16;
-    pa.n[1] = 31;
-    pa.n[2] = cg;
-    pa.n[3] = cg;
-    HIPCK(pack_strided(pa, e->mstream));
+    RC(dalloc(e, kConvPackElems * e->esz, &e->conv_w[j]));
+    RC(pack_conv_weight(w->p, w->dt, d, e->conv_w[j], op_dt(e), e->mstream));
     RC(vec_upload(e, W, p + "bias", d, &e->conv_b[j], &err));
   }
   // blocks
@@ -2131,9 +2142,9 @@ int f5h_debug_tile_live(const int32_t* live_len, int32_t live_seq, int32_t M, in
   return tile_live_rows(live_len, live_seq, M, m0, BM) ? 1 : 0;
 }
 
-int f5h_op_attention(void* stream, int32_t compute, int32_t S, int32_t H, int32_t N, const float* Q, const float* K,
-                     const float* V, const int32_t* kv_len, int32_t q_prescaled, float* O, void* workspace,
-                     size_t workspace_bytes) {
+static int op_attention_impl(void* stream, int32_t compute, int32_t S, int32_t H, int32_t N, const float* Q,
+                             const float* K, const float* V, const int32_t* kv_len, const int32_t* q_len,
+                             int32_t q_prescaled, float* O, void* workspace, size_t workspace_bytes) {
   if (S <= 0 || H <= 0 || N <= 0) return fail(F5H_EINVAL, "bad attention shape");
   if (compute < F5H_FP32 || compute > F5H_FP16) return fail(F5H_EINVAL, "bad compute mode");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -2143,6 +2154,7 @@ int f5h_op_attention(void* stream, int32_t compute, int32_t S, int32_t H, int32_
   at.H = H;
   at.L = N;
   at.kv_len = kv_len;
+  at.q_len = q_len;
   at.scale = 0.125f;
   at.prescaled = q_prescaled ? 1 : 0;
   if (compute) {
@@ -2165,6 +2177,282 @@ int f5h_op_attention(void* stream, int32_t compute, int32_t S, int32_t H, int32_
     at.v = V;
     at.o = O;
     HIPCK(attention(0, at, st));
+  }
+  return 0;
+}
+
+int f5h_op_attention(void* stream, int32_t compute, int32_t S, int32_t H, int32_t N, const float* Q, const float* K,
+                     const float* V, const int32_t* kv_len, int32_t q_prescaled, float* O, void* workspace,
+                     size_t workspace_bytes) {
+  return op_attention_impl(stream, compute, S, H, N, Q, K, V, kv_len, nullptr, q_prescaled, O, workspace,
+                           workspace_bytes);
+}
+
+int f5h_op_attention_qlen(void* stream, int32_t compute, int32_t S, int32_t H, int32_t N, const float* Q,
+                          const float* K, const float* V, const int32_t* kv_len, const int32_t* q_len,
+                          int32_t q_prescaled, float* O, void* workspace, size_t workspace_bytes) {
+  return op_attention_impl(stream, compute, S, H, N, Q, K, V, kv_len, q_len, q_prescaled, O, workspace,
+                           workspace_bytes);
+}
+
+// ---- op-level entry points of the conv / norm / GEMM-epilogue kernels (tests/test_gpu_ops.py). Each validates
+// its shapes on the host (F5H_EINVAL, nothing enqueued), stages the operand-dtype buffers the kernel's contract
+// asks for in the caller's workspace (f32_to_op / op_to_f32), calls the production launcher unchanged and
+// returns fp32. A buffer the kernel writes in the operand dtype starts as the rounded copy of the caller's
+// fp32 buffer, so elements the kernel leaves alone come back as they went in.
+static bool op_compute_ok(int32_t compute) { return compute >= F5H_FP32 && compute <= F5H_FP16; }
+// caller workspace as a bump allocator: null when it does not fit (fits() then fails the call)
+struct OpWs {
+  WS ws;
+  size_t bytes;
+  OpWs(void* base, size_t n) : bytes(n) { ws.base = reinterpret_cast<char*>(base); }
+  void* take(size_t n) { return ws.take<char>(n); }
+  bool fits() const { return ws.off == 0 || (ws.base && ws.off <= bytes); }
+};
+#define OPWS_CHECK(w, what)                                                                       \
+  do {                                                                                            \
+    if (!(w).fits()) return fail(F5H_ENOMEM, std::string("workspace too small for ") + (what));  \
+  } while (0)
+
+int f5h_op_conv_pos(void* stream, int32_t compute, int32_t S, int32_t L, int32_t d, const float* x, const float* w,
+                    const float* bias, const uint8_t* rowkeep, int32_t mode, const float* resid, int32_t x_as_f32,
+                    int64_t y_seq_stride, int64_t y_row_off, float* y, void* workspace, size_t workspace_bytes) {
+  if (!op_compute_ok(compute)) return fail(F5H_EINVAL, "bad compute mode");
+  if (S <= 0 || L <= 0 || d <= 0) return fail(F5H_EINVAL, "op_conv_pos: bad shape");
+  if (d % 128 || d > 1024) return fail(F5H_EINVAL, "op_conv_pos needs d % 128 == 0 and d <= 1024");
+  if ((int64_t)S * L * d >= (int64_t)1 << 31) return fail(F5H_EINVAL, "op_conv_pos: S * L * d must stay below 2^31");
+  if (mode < 0 || mode > 2) return fail(F5H_EINVAL, "op_conv_pos: mode must be 0, 1 or 2");
+  if (mode == 2 && !compute) return fail(F5H_EINVAL, "op_conv_pos: mode 2 writes the 16-bit residual stream");
+  if (!x || !w || !bias || !y) return fail(F5H_EINVAL, "op_conv_pos: null tensor");
+  if (mode != 0 && !resid) return fail(F5H_EINVAL, "op_conv_pos: modes 1 and 2 add a residual");
+  // mode 0 writes a dense [S, L, d] (the kernel ignores the row placement there)
+  if (mode == 0 && (y_row_off != 0 || y_seq_stride != L))
+    return fail(F5H_EINVAL, "op_conv_pos: mode 0 takes y_row_off 0 and y_seq_stride L");
+  if (y_row_off < 0 || y_seq_stride < y_row_off + L) return fail(F5H_EINVAL, "op_conv_pos: rows outside y");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const size_t es = compute ? 2 : 4;
+  const int64_t nx = (int64_t)S * L * d, ny = (int64_t)S * y_seq_stride * d;
+  OpWs ws(workspace, workspace_bytes);
+  void* wp = ws.take(kConvPackElems * es);
+  void* xop = (compute && !x_as_f32) ? ws.take((size_t)nx * es) : nullptr;
+  const bool y16 = compute && mode != 1;
+  void* yop = y16 ? ws.take((size_t)ny * es) : nullptr;
+  OPWS_CHECK(ws, "op_conv_pos");
+  HIPCK(hipMemsetAsync(wp, 0, kConvPackElems * es, st));
+  RC(pack_conv_weight(w, F5H_DT_F32, d, wp, compute, st));
+  ConvArgs cv{};
+  cv.S = S;
+  cv.L = L;
+  cv.d = d;
+  cv.x = x;
+  cv.x_f32 = 1;
+  if (xop) {
+    HIPCK(f32_to_op(compute, x, nx, xop, st));
+    cv.x = xop;
+    cv.x_f32 = 0;
+  }
+  cv.w = wp;
+  cv.bias = bias;
+  cv.rowkeep = rowkeep;
+  cv.mode = mode;
+  cv.y = y;
+  if (yop) {
+    HIPCK(f32_to_op(compute, y, ny, yop, st));
+    cv.y = yop;
+  }
+  cv.y_seq_stride = y_seq_stride;
+  cv.y_row_off = y_row_off;
+  cv.resid = resid;
+  HIPCK(conv_pos(compute, cv, st));
+  if (yop) HIPCK(op_to_f32(compute, yop, ny, y, st));
+  return 0;
+}
+
+int f5h_op_norm(void* stream, int32_t compute, int32_t kind, int32_t h16, int32_t M, int32_t d, const float* h,
+                const float* shift_or_g, const float* scale, float* out, void* workspace, size_t workspace_bytes) {
+  if (!op_compute_ok(compute)) return fail(F5H_EINVAL, "bad compute mode");
+  if (kind != 0 && kind != 1) return fail(F5H_EINVAL, "op_norm: kind must be 0 (LayerNorm-modulate) or 1 (RMSNorm)");
+  if (M <= 0 || d <= 0) return fail(F5H_EINVAL, "op_norm: bad shape");
+  if (d % 4 || d > 2048) return fail(F5H_EINVAL, "op_norm needs d % 4 == 0 and d <= 2048");
+  if (h16 && !compute) return fail(F5H_EINVAL, "op_norm: a 16-bit h needs a 16-bit compute mode");
+  if (!h || !shift_or_g || !out || (kind == 0 && !scale)) return fail(F5H_EINVAL, "op_norm: null tensor");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t n = (int64_t)M * d;
+  OpWs ws(workspace, workspace_bytes);
+  void* hop = h16 ? ws.take((size_t)n * 2) : nullptr;
+  void* oop = compute ? ws.take((size_t)n * 2) : nullptr;
+  OPWS_CHECK(ws, "op_norm");
+  const void* hin = h;
+  if (hop) {
+    HIPCK(f32_to_op(compute, h, n, hop, st));
+    hin = hop;
+  }
+  void* o = oop ? oop : (void*)out;
+  if (kind == 0)
+    HIPCK(ln_modulate(compute, hin, h16 ? 1 : 0, M, d, shift_or_g, scale, o, st));
+  else
+    HIPCK(rms_norm_g(compute, hin, h16 ? 1 : 0, M, d, shift_or_g, o, st));
+  if (oop) HIPCK(op_to_f32(compute, oop, n, out, st));
+  return 0;
+}
+
+int f5h_op_dwconv_ln(void* stream, int32_t compute, int32_t S, int32_t L, int32_t C, const float* x,
+                     const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b, float* out,
+                     void* workspace, size_t workspace_bytes) {
+  if (!op_compute_ok(compute)) return fail(F5H_EINVAL, "bad compute mode");
+  if (S <= 0 || L <= 0 || C <= 0) return fail(F5H_EINVAL, "op_dwconv_ln: bad shape");
+  if (C > 1024) return fail(F5H_EINVAL, "op_dwconv_ln needs C <= 1024");
+  if ((int64_t)S * L >= (int64_t)1 << 30) return fail(F5H_EINVAL, "op_dwconv_ln: too many rows");
+  if (!x || !dw_w || !dw_b || !ln_w || !ln_b || !out) return fail(F5H_EINVAL, "op_dwconv_ln: null tensor");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t n = (int64_t)S * L * C;
+  OpWs ws(workspace, workspace_bytes);
+  void* oop = compute ? ws.take((size_t)n * 2) : nullptr;
+  OPWS_CHECK(ws, "op_dwconv_ln");
+  HIPCK(dwconv_ln(compute, x, S, L, C, dw_w, dw_b, ln_w, ln_b, oop ? oop : (void*)out, st));
+  if (oop) HIPCK(op_to_f32(compute, oop, n, out, st));
+  return 0;
+}
+
+int f5h_op_grn(void* stream, int32_t compute, int32_t S, int32_t L, int32_t C, const float* x, const float* gamma,
+               const float* beta, float* out, void* workspace, size_t workspace_bytes) {
+  if (!op_compute_ok(compute)) return fail(F5H_EINVAL, "bad compute mode");
+  if (S <= 0 || L <= 0 || C <= 0) return fail(F5H_EINVAL, "op_grn: bad shape");
+  if (S > 65535 || (L + 63) / 64 > 65535) return fail(F5H_EINVAL, "op_grn: S and L / 64 are grid dimensions");
+  if (!x || !gamma || !beta || !out) return fail(F5H_EINVAL, "op_grn: null tensor");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t n = (int64_t)S * L * C;
+  OpWs ws(workspace, workspace_bytes);
+  float* scratch = reinterpret_cast<float*>(ws.take(((size_t)(L + 63) / 64 + 1) * S * C * sizeof(float)));
+  void* oop = compute ? ws.take((size_t)n * 2) : nullptr;
+  OPWS_CHECK(ws, "op_grn");
+  HIPCK(grn(compute, x, S, L, C, gamma, beta, scratch, oop ? oop : (void*)out, st));
+  if (oop) HIPCK(op_to_f32(compute, oop, n, out, st));
+  return 0;
+}
+
+int f5h_op_gemm_epi(void* stream, const f5h_op_gemm_args* a, void* workspace, size_t workspace_bytes) {
+  if (!a) return fail(F5H_EINVAL, "op_gemm_epi: null args");
+  const int compute = a->compute, epi = a->epi, M = a->M, N = a->N, K = a->K;
+  if (!op_compute_ok(compute)) return fail(F5H_EINVAL, "bad compute mode");
+  if (epi < EPI_STORE || epi > EPI_STORE16) return fail(F5H_EINVAL, "op_gemm_epi: unknown epilogue");
+  if (M <= 0 || N <= 0 || K <= 0) return fail(F5H_EINVAL, "op_gemm_epi: bad shape");
+  if (K % 64) return fail(F5H_EINVAL, "op_gemm_epi needs K % 64 == 0");
+  if (!a->A || !a->W) return fail(F5H_EINVAL, "op_gemm_epi: null operand");
+  if (a->A2 && (a->k_split <= 0 || a->k_split % 64 || a->k_split >= K))
+    return fail(F5H_EINVAL, "op_gemm_epi: k_split must be a multiple of 64 inside (0, K)");
+  const bool resid_epi = epi == EPI_RESID || epi == EPI_RESID16;
+  const bool inout = resid_epi || epi == EPI_RESID_FILL;
+  if (a->resid && !resid_epi) return fail(F5H_EINVAL, "op_gemm_epi: resid goes with EPI_RESID / EPI_RESID16");
+  if (a->gate && !resid_epi) return fail(F5H_EINVAL, "op_gemm_epi: gate goes with EPI_RESID / EPI_RESID16");
+  if (a->rowkeep && !inout) return fail(F5H_EINVAL, "op_gemm_epi: rowkeep goes with the in/out epilogues");
+  if (a->live_len) {
+    // the pad-row skip: in place only (a skipped tile leaves C as it was), rows described by rowkeep as well
+    if (!resid_epi || a->resid || !a->rowkeep || a->live_seq <= 0 || M % a->live_seq)
+      return fail(F5H_EINVAL, "op_gemm_epi: live_len needs an in-place EPI_RESID(16) with rowkeep and M % live_seq == 0");
+  }
+  int64_t dual = 0;
+  if (epi == EPI_INPROJ) {
+    if (N % 8 || !a->add || a->ld_add < N || a->ld_add % 8 || a->dual_rows < 0 || a->bias)
+      return fail(F5H_EINVAL, "op_gemm_epi: EPI_INPROJ needs N % 8 == 0, an addend with ld_add % 8 == 0 and no bias");
+    dual = a->dual_rows;
+    if (dual != 0 && dual < M) return fail(F5H_EINVAL, "op_gemm_epi: dual_rows must be 0 or >= M");
+  } else if (a->add || a->dual_rows) {
+    return fail(F5H_EINVAL, "op_gemm_epi: add / dual_rows go with EPI_INPROJ");
+  }
+  int inner = 0;
+  if (epi == EPI_QKV) {
+    inner = a->heads * 64;
+    if (a->heads <= 0 || N != 3 * inner || a->seq_len <= 0 || M % a->seq_len || a->rope_heads < 0 ||
+        a->rope_heads > a->heads || !a->q || !a->k || !a->v)
+      return fail(F5H_EINVAL, "op_gemm_epi: EPI_QKV needs N == 3 * heads * 64, M % seq_len == 0 and q, k, v");
+  } else if (!a->C) {
+    return fail(F5H_EINVAL, "op_gemm_epi: null C");
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const size_t es = compute ? 2 : 4;
+  const int Npad = (N + 127) / 128 * 128;
+  // output element type: the operand dtype for these, fp32 otherwise
+  const bool out_op = epi == EPI_GELU_TANH || epi == EPI_GELU_ERF_OP || epi == EPI_RESID16 || epi == EPI_STORE16;
+  const int64_t nC = (int64_t)(M + dual) * N, nA = (int64_t)M * K, nqkv = (int64_t)M * inner;
+  OpWs ws(workspace, workspace_bytes);
+  void* wop = ws.take((size_t)Npad * K * es);
+  void* aop = compute ? ws.take((size_t)nA * es) : nullptr;
+  void* a2op = (compute && a->A2) ? ws.take((size_t)nA * es) : nullptr;
+  void* cop = (compute && out_op) ? ws.take((size_t)nC * es) : nullptr;
+  void* rop = (compute && epi == EPI_RESID16 && a->resid) ? ws.take((size_t)nC * es) : nullptr;
+  void *qop = nullptr, *kop = nullptr, *vop = nullptr;
+  float2* rope = nullptr;
+  if (epi == EPI_QKV) {
+    rope = reinterpret_cast<float2*>(ws.take((size_t)a->seq_len * 32 * sizeof(float2)));
+    if (compute) {
+      qop = ws.take((size_t)nqkv * es);
+      kop = ws.take((size_t)nqkv * es);
+      vop = ws.take((size_t)nqkv * es);
+    }
+  }
+  OPWS_CHECK(ws, "op_gemm_epi");
+  HIPCK(hipMemsetAsync(wop, 0, (size_t)Npad * K * es, st));
+  HIPCK(f32_to_op(compute, a->W, (int64_t)N * K, wop, st));
+  GemmArgs g{};
+  g.A = a->A;
+  g.A2 = a->A2;
+  if (aop) {
+    HIPCK(f32_to_op(compute, a->A, nA, aop, st));
+    g.A = aop;
+  }
+  if (a2op) {
+    HIPCK(f32_to_op(compute, a->A2, nA, a2op, st));
+    g.A2 = a2op;
+  }
+  g.k_split = a->A2 ? a->k_split : 0;
+  g.lda = K;
+  g.W = wop;
+  g.ldw = K;
+  g.M = M;
+  g.N = N;
+  g.K = K;
+  g.bias = a->bias;
+  g.C = a->C;
+  g.ldc = N;
+  g.gate = a->gate;
+  g.rowkeep = a->rowkeep;
+  g.resid = a->resid;
+  g.live_len = a->live_len;
+  g.live_seq = a->live_len ? a->live_seq : 0;
+  g.add = a->add;
+  g.ld_add = a->ld_add;
+  g.dual_rows = dual;
+  if (cop) {
+    // in/out (EPI_RESID16): the rounded C goes in; write-only epilogues overwrite every element
+    if (inout) HIPCK(f32_to_op(compute, a->C, nC, cop, st));
+    g.C = cop;
+  }
+  if (rop) {
+    HIPCK(f32_to_op(compute, a->resid, nC, rop, st));
+    g.resid = rop;
+  }
+  if (epi == EPI_QKV) {
+    HIPCK(rope_table(a->seq_len, rope, st));
+    if (a->rope_out)
+      HIPCK(hipMemcpyAsync(a->rope_out, rope, (size_t)a->seq_len * 32 * sizeof(float2), hipMemcpyDeviceToDevice, st));
+    g.rope = rope;
+    g.seq_len = a->seq_len;
+    g.heads = a->heads;
+    g.rope_heads = a->rope_heads > 0 ? a->rope_heads : a->heads;
+    g.q_scale = a->q_scale;
+    g.q = compute ? qop : (void*)a->q;
+    g.k = compute ? kop : (void*)a->k;
+    g.v = compute ? vop : (void*)a->v;
+    g.C = nullptr;
+    g.ldc = 0;
+  }
+  HIPCK(gemm(compute, epi, g, st));
+  if (cop) HIPCK(op_to_f32(compute, cop, nC, a->C, st));
+  if (epi == EPI_QKV && compute) {
+    HIPCK(op_to_f32(compute, qop, nqkv, a->q, st));
+    HIPCK(op_to_f32(compute, kop, nqkv, a->k, st));
+    HIPCK(op_to_f32(compute, vop, nqkv, a->v, st));
   }
   return 0;
 }

@@ -53,6 +53,12 @@ EXPORTS = (
     "f5h_ln_fold_stats",
     "f5h_op_linear",
     "f5h_op_attention",
+    "f5h_op_attention_qlen",
+    "f5h_op_conv_pos",
+    "f5h_op_norm",
+    "f5h_op_dwconv_ln",
+    "f5h_op_grn",
+    "f5h_op_gemm_epi",
     "f5h_gemm_force_config",
     "f5h_attn_force_safe",
     "f5h_debug_tile_live",
@@ -113,6 +119,20 @@ class ForwardArgs(ctypes.Structure):
         ("use_batch_mask", ctypes.c_int32), ("pred", ctypes.c_void_p),
         ("cfg_infer", ctypes.c_int32), ("drop_audio_cond", ctypes.c_int32), ("drop_text", ctypes.c_int32),
         ("t_dev", ctypes.c_void_p), ("text_cache", ctypes.c_int32),
+    ]
+
+
+class OpGemmArgs(ctypes.Structure):
+    _fields_ = [
+        ("compute", ctypes.c_int32), ("epi", ctypes.c_int32), ("M", ctypes.c_int32), ("N", ctypes.c_int32),
+        ("K", ctypes.c_int32), ("k_split", ctypes.c_int32),
+        ("A", ctypes.c_void_p), ("A2", ctypes.c_void_p), ("W", ctypes.c_void_p), ("bias", ctypes.c_void_p),
+        ("C", ctypes.c_void_p), ("resid", ctypes.c_void_p), ("gate", ctypes.c_void_p), ("rowkeep", ctypes.c_void_p),
+        ("live_len", ctypes.c_void_p), ("live_seq", ctypes.c_int32),
+        ("seq_len", ctypes.c_int32), ("heads", ctypes.c_int32), ("rope_heads", ctypes.c_int32),
+        ("q_scale", ctypes.c_float),
+        ("add", ctypes.c_void_p), ("ld_add", ctypes.c_int64), ("dual_rows", ctypes.c_int64),
+        ("q", ctypes.c_void_p), ("k", ctypes.c_void_p), ("v", ctypes.c_void_p), ("rope_out", ctypes.c_void_p),
     ]
 
 
@@ -180,6 +200,19 @@ def lib():
     L.f5h_op_linear.restype = ctypes.c_int
     L.f5h_op_attention.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, sz]
     L.f5h_op_attention.restype = ctypes.c_int
+    if hasattr(L, "f5h_op_gemm_epi"):  # op-level test entry points (absent from an older build, F5H_LIB)
+        L.f5h_op_attention_qlen.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, sz]
+        L.f5h_op_attention_qlen.restype = ctypes.c_int
+        L.f5h_op_conv_pos.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, i32, i64, i64, vp, vp, sz]
+        L.f5h_op_conv_pos.restype = ctypes.c_int
+        L.f5h_op_norm.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz]
+        L.f5h_op_norm.restype = ctypes.c_int
+        L.f5h_op_dwconv_ln.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz]
+        L.f5h_op_dwconv_ln.restype = ctypes.c_int
+        L.f5h_op_grn.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz]
+        L.f5h_op_grn.restype = ctypes.c_int
+        L.f5h_op_gemm_epi.argtypes = [vp, ctypes.POINTER(OpGemmArgs), vp, sz]
+        L.f5h_op_gemm_epi.restype = ctypes.c_int
     L.f5h_gemm_force_config.argtypes = [i32]
     L.f5h_gemm_force_config.restype = ctypes.c_int
     # test hooks: bound when present, so an older build loaded through F5H_LIB (one-box A/Bs) still loads

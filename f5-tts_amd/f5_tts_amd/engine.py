@@ -308,10 +308,12 @@ def op_linear(A, W, bias=None, compute="bf16"):
     return C
 
 
-def op_attention(Q, K, V, kv_len=None, compute="bf16", q_prescaled=False, poison=False):
+def op_attention(Q, K, V, kv_len=None, compute="bf16", q_prescaled=False, poison=False, q_len=None):
     """O[S,N,H*64] = softmax(Q K^T/8) V; q_prescaled: Q already carries (1/8)*log2(e). poison: fill the
     workspace (16-bit q | k | v | o, back to back) with NaN bits first, so a kernel that reads key rows past N
-    (the next (sequence, head)'s rows, or past V into O) turns its output NaN."""
+    (the next (sequence, head)'s rows, or past V into O) turns its output NaN. q_len [S]: live query rows per
+    sequence (the batch path's pad skip); with poison, O is NaN as well before the call, so rows the kernel
+    leaves unwritten come back NaN in every compute mode."""
     S, H, N, D = Q.shape
     assert D == 64
     O = torch.empty(S, N, H * 64, dtype=torch.float32, device=Q.device)
@@ -319,11 +321,131 @@ def op_attention(Q, K, V, kv_len=None, compute="bf16", q_prescaled=False, poison
     if poison:
         ws.fill_(0xFF)
     kv = None if kv_len is None else kv_len.to(Q.device, torch.int32).contiguous()
-    _lib.check(_lib.lib().f5h_op_attention(_lib.stream_handle(Q.device), _lib.COMPUTE[compute], S, H, N,
-                                           Q.contiguous().data_ptr(), K.contiguous().data_ptr(),
-                                           V.contiguous().data_ptr(), _lib.ptr(kv), int(bool(q_prescaled)),
-                                           O.data_ptr(), ws.data_ptr(), ws.numel()), "f5h_op_attention")
+    if q_len is None:
+        _lib.check(_lib.lib().f5h_op_attention(_lib.stream_handle(Q.device), _lib.COMPUTE[compute], S, H, N,
+                                               Q.contiguous().data_ptr(), K.contiguous().data_ptr(),
+                                               V.contiguous().data_ptr(), _lib.ptr(kv), int(bool(q_prescaled)),
+                                               O.data_ptr(), ws.data_ptr(), ws.numel()), "f5h_op_attention")
+        return O
+    if poison:
+        O.fill_(float("nan"))
+    ql = q_len.to(Q.device, torch.int32).contiguous()
+    _lib.check(_lib.lib().f5h_op_attention_qlen(_lib.stream_handle(Q.device), _lib.COMPUTE[compute], S, H, N,
+                                                Q.contiguous().data_ptr(), K.contiguous().data_ptr(),
+                                                V.contiguous().data_ptr(), _lib.ptr(kv), ql.data_ptr(),
+                                                int(bool(q_prescaled)), O.data_ptr(), ws.data_ptr(), ws.numel()),
+               "f5h_op_attention_qlen")
     return O
+
+
+def _f32(t, dev=None):
+    return None if t is None else t.to(device=dev or t.device, dtype=torch.float32).contiguous()
+
+
+def _u8(t, dev):
+    return None if t is None else t.to(device=dev, dtype=torch.uint8).contiguous()
+
+
+def op_conv_pos(x, w, bias, rowkeep=None, mode=0, resid=None, x_as_f32=True, y=None, y_row_off=0, compute="bf16"):
+    """One ConvPositionEmbedding layer (f5h_op_conv_pos): x [S,L,d], w [d, d/16, 31], bias [d], rowkeep [S,L] or
+    None. mode 0 returns y [S,L,d]; modes 1 / 2 write rows y_row_off.. of each sequence of `y` [S, rows, d] in
+    place (a fresh [S, L + y_row_off, d] of NaN when None) and return it."""
+    S, L, d = x.shape
+    dev = x.device
+    x, w, bias, resid = _f32(x), _f32(w, dev), _f32(bias, dev), _f32(resid, dev)
+    if y is None:
+        y = torch.full((S, L + (y_row_off if mode else 0), d), float("nan"), dtype=torch.float32, device=dev)
+    assert y.is_contiguous() and y.dtype == torch.float32
+    keep = _u8(rowkeep, dev)
+    ws = torch.empty(16 * 31 * 64 * 64 * 4 + x.numel() * 2 + y.numel() * 2 + 1024, dtype=torch.uint8, device=dev)
+    _lib.check(_lib.lib().f5h_op_conv_pos(_lib.stream_handle(dev), _lib.COMPUTE[compute], S, L, d, x.data_ptr(),
+                                          w.data_ptr(), bias.data_ptr(), _lib.ptr(keep), int(mode),
+                                          _lib.ptr(resid), int(bool(x_as_f32)), y.shape[1], int(y_row_off),
+                                          y.data_ptr(), ws.data_ptr(), ws.numel()), "f5h_op_conv_pos")
+    return y
+
+
+def op_norm(kind, h, p0, p1=None, h16=False, compute="bf16"):
+    """kind "ln": LayerNorm(h) * (1 + p1) + p0 (p0 shift, p1 scale); kind "rms": RMSNorm with gain p0. h [M,d]."""
+    M, d = h.shape
+    dev = h.device
+    h, p0, p1 = _f32(h), _f32(p0, dev), _f32(p1, dev)
+    out = torch.empty(M, d, dtype=torch.float32, device=dev)
+    ws = torch.empty(h.numel() * 4 + 1024, dtype=torch.uint8, device=dev)
+    _lib.check(_lib.lib().f5h_op_norm(_lib.stream_handle(dev), _lib.COMPUTE[compute], {"ln": 0, "rms": 1}[kind],
+                                      int(bool(h16)), M, d, h.data_ptr(), p0.data_ptr(), _lib.ptr(p1),
+                                      out.data_ptr(), ws.data_ptr(), ws.numel()), "f5h_op_norm")
+    return out
+
+
+def op_dwconv_ln(x, dw_w, dw_b, ln_w, ln_b, compute="bf16"):
+    """LayerNorm(dwconv7(x) + dw_b) * ln_w + ln_b; x [S,L,C], dw_w [C,7]."""
+    S, L, C = x.shape
+    dev = x.device
+    x, dw_w, dw_b, ln_w, ln_b = (_f32(t, dev) for t in (x, dw_w, dw_b, ln_w, ln_b))
+    out = torch.empty(S, L, C, dtype=torch.float32, device=dev)
+    ws = torch.empty(x.numel() * 2 + 1024, dtype=torch.uint8, device=dev)
+    _lib.check(_lib.lib().f5h_op_dwconv_ln(_lib.stream_handle(dev), _lib.COMPUTE[compute], S, L, C, x.data_ptr(),
+                                           dw_w.data_ptr(), dw_b.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(),
+                                           out.data_ptr(), ws.data_ptr(), ws.numel()), "f5h_op_dwconv_ln")
+    return out
+
+
+def op_grn(x, gamma, beta, compute="bf16"):
+    """GRN over time: gamma * (x * Nx) + beta + x; x [S,L,C]."""
+    S, L, C = x.shape
+    dev = x.device
+    x, gamma, beta = (_f32(t, dev) for t in (x, gamma, beta))
+    out = torch.empty(S, L, C, dtype=torch.float32, device=dev)
+    ws = torch.empty(((L + 63) // 64 + 1) * S * C * 4 + x.numel() * 2 + 1024, dtype=torch.uint8, device=dev)
+    _lib.check(_lib.lib().f5h_op_grn(_lib.stream_handle(dev), _lib.COMPUTE[compute], S, L, C, x.data_ptr(),
+                                     gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel()),
+               "f5h_op_grn")
+    return out
+
+
+EPI = {"store": 0, "silu": 1, "gelu_tanh": 2, "gelu_erf": 3, "resid": 4, "resid_fill": 5, "inproj": 6, "qkv": 7,
+       "gelu_erf_op": 8, "resid16": 9, "store16": 10}
+
+
+def op_gemm_epi(epi, A, W, bias=None, C=None, compute="bf16", A2=None, k_split=0, resid=None, gate=None, rowkeep=None,
+                live_len=None, live_seq=0, add=None, dual_rows=0, seq_len=0, heads=0, rope_heads=0, q_scale=0.0):
+    """A GEMM with epilogue `epi` (a key of EPI; f5h_op_gemm_epi). The in/out epilogues update a copy of C and
+    return it; "inproj" returns C [M + dual_rows, N]; "qkv" returns (q, k, v [S,H,L,64], rope [L,32,2])."""
+    M, K = A.shape
+    N = W.shape[0]
+    dev = A.device
+    A, A2, W, bias, resid, gate, add = (_f32(t, dev) for t in (A, A2, W, bias, resid, gate, add))
+    keep = _u8(rowkeep, dev)
+    ll = None if live_len is None else live_len.to(dev, torch.int32).contiguous()
+    a = _lib.OpGemmArgs()
+    a.compute, a.epi, a.M, a.N, a.K, a.k_split = _lib.COMPUTE[compute], EPI[epi], M, N, K, int(k_split)
+    a.A, a.A2, a.W, a.bias = A.data_ptr(), _lib.ptr(A2), W.data_ptr(), _lib.ptr(bias)
+    a.resid, a.gate, a.rowkeep, a.live_len, a.live_seq = _lib.ptr(resid), _lib.ptr(gate), _lib.ptr(keep), \
+        _lib.ptr(ll), int(live_seq)
+    a.add, a.ld_add, a.dual_rows = _lib.ptr(add), (0 if add is None else add.shape[1]), int(dual_rows)
+    ws_bytes = ((N + 127) // 128 * 128) * K * 4 + 3 * M * K * 4 + 3 * (M + int(dual_rows)) * N * 4 + 4096
+    out = None
+    if epi == "qkv":
+        S = M // seq_len if seq_len > 0 else 0
+        q, k, v = (torch.full((S, heads, seq_len, 64), float("nan"), dtype=torch.float32, device=dev)
+                   for _ in range(3))
+        rope = torch.empty(max(seq_len, 0), 32, 2, dtype=torch.float32, device=dev)
+        a.seq_len, a.heads, a.rope_heads, a.q_scale = int(seq_len), int(heads), int(rope_heads), float(q_scale)
+        a.q, a.k, a.v, a.rope_out = q.data_ptr(), k.data_ptr(), v.data_ptr(), rope.data_ptr()
+        ws_bytes += max(seq_len, 0) * 256 + 1024
+        out = (q, k, v, rope)
+    else:
+        if C is None:
+            C = torch.full((M + int(dual_rows), N), float("nan"), dtype=torch.float32, device=dev)
+        else:
+            C = _f32(C, dev).clone()
+        a.C = C.data_ptr()
+        out = C
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    _lib.check(_lib.lib().f5h_op_gemm_epi(_lib.stream_handle(dev), ctypes.byref(a), ws.data_ptr(), ws.numel()),
+               "f5h_op_gemm_epi")
+    return out
 
 
 def attn_force_safe(on: bool):

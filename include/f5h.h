@@ -293,6 +293,84 @@ int f5h_op_linear(void* stream, int32_t compute, int32_t M, int32_t N, int32_t K
 int f5h_op_attention(void* stream, int32_t compute, int32_t S, int32_t H, int32_t N, const float* Q,
                      const float* K, const float* V, const int32_t* kv_len, int32_t q_prescaled, float* O,
                      void* workspace, size_t workspace_bytes);
+/* The same with q_len: [S] live query rows per sequence or NULL. Rows [q_len[s], N) are dead: a skip unit (a
+ * 64-row block in the fp32 mode, a 32-row wave in the 16-bit modes) wholly past q_len[s] leaves its rows of O
+ * unwritten, one that straddles it writes all of its rows. In the 16-bit modes the kernel writes the 16-bit O at
+ * workspace byte 6 * S*H*N*64, which is then converted to `O` whole: unwritten rows show what the caller left
+ * there. */
+int f5h_op_attention_qlen(void* stream, int32_t compute, int32_t S, int32_t H, int32_t N, const float* Q,
+                          const float* K, const float* V, const int32_t* kv_len, const int32_t* q_len,
+                          int32_t q_prescaled, float* O, void* workspace, size_t workspace_bytes);
+
+/* Op-level entry points of the conv, norm and GEMM-epilogue kernels (tests/test_gpu_ops.py). fp32 device tensors
+ * in and out; buffers a kernel reads or writes in the operand dtype are staged in `workspace` (rounded to nearest
+ * even); the production launcher runs unchanged. A buffer the kernel writes in the operand dtype starts as the
+ * rounded copy of the caller's fp32 buffer, so elements the kernel leaves alone come back as they went in. Shapes
+ * outside a launcher's contract return F5H_EINVAL before any device work, a short workspace F5H_ENOMEM.
+ *
+ * ConvPositionEmbedding layer (modules.py:175-201): y = mish(where(keep, conv(where(keep, x, 0)) + bias, 0))
+ * [+ resid], Conv1d(d, d, k 31, 16 groups, pad 15) per sequence. x [S,L,d]; w [d, d/16, 31] (torch layout, packed
+ * as engine creation packs it); bias [d]; rowkeep [S*L] bytes or NULL. mode 0: y [S,L,d] in the operand dtype
+ * (y_seq_stride = L, y_row_off = 0); mode 1: y fp32 = .. + resid; mode 2 (16-bit modes): y operand dtype = .. +
+ * resid; modes 1, 2 write row y_row_off + n of sequence s in y [S, y_seq_stride, d]; resid [S,L,d] fp32.
+ * x_as_f32 (16-bit modes): the kernel reads the fp32 x and rounds it itself; 0: it reads x rounded beforehand.
+ * d % 128 == 0, d <= 1024. */
+int f5h_op_conv_pos(void* stream, int32_t compute, int32_t S, int32_t L, int32_t d, const float* x, const float* w,
+                    const float* bias, const uint8_t* rowkeep, int32_t mode, const float* resid, int32_t x_as_f32,
+                    int64_t y_seq_stride, int64_t y_row_off, float* y, void* workspace, size_t workspace_bytes);
+/* Row norms, h [M,d] -> out [M,d] (operand dtype). kind 0: LayerNorm(eps 1e-6, no affine) * (1 + scale) + shift
+ * with shift_or_g = shift [d], scale [d] (modules.py:325, 346); kind 1: x_transformers RMSNorm
+ * h / max(|h|, 1e-12) * sqrt(d) * g with shift_or_g = g [d] (scale ignored). h16 (16-bit modes): the kernel reads
+ * h in the operand dtype (the 16-bit residual stream). d % 4 == 0, d <= 2048. */
+int f5h_op_norm(void* stream, int32_t compute, int32_t kind, int32_t h16, int32_t M, int32_t d, const float* h,
+                const float* shift_or_g, const float* scale, float* out, void* workspace, size_t workspace_bytes);
+/* ConvNeXtV2Block front half (modules.py:260-264, 273-275): depthwise Conv1d(k 7, pad 3) + bias, then
+ * LayerNorm(affine, eps 1e-6). x [S,L,C]; dw_w [C,7]; dw_b, ln_w, ln_b [C]; out [S,L,C] (operand dtype). C <= 1024. */
+int f5h_op_dwconv_ln(void* stream, int32_t compute, int32_t S, int32_t L, int32_t C, const float* x,
+                     const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b, float* out,
+                     void* workspace, size_t workspace_bytes);
+/* GRN (modules.py:236-245): Gx = |x|_2 over time, Nx = Gx / (mean_c Gx + 1e-6), out = gamma (x Nx) + beta + x.
+ * x [S,L,C]; gamma, beta [C]; out [S,L,C] (operand dtype). */
+int f5h_op_grn(void* stream, int32_t compute, int32_t S, int32_t L, int32_t C, const float* x, const float* gamma,
+               const float* beta, float* out, void* workspace, size_t workspace_bytes);
+
+/* f5h_op_linear with any GEMM epilogue but the LayerNorm / RMSNorm fold forms. epi:
+ *   0 STORE       C = acc + bias                          1 SILU          C = silu(acc + bias)
+ *   2 GELU_TANH   C = gelu_tanh(acc + bias)  (operand)    3 GELU_ERF      C = gelu_erf(acc + bias)
+ *   4 RESID       C = keep[m] ? R + gate[n] (acc + bias) : R, R = resid or C
+ *   5 RESID_FILL  C = keep[m] ? C + acc + bias : 0
+ *   6 INPROJ      C[m] = acc + add[m]; with dual_rows, C[m + dual_rows] = acc + add[m + dual_rows]
+ *   7 QKV         columns [q | k | v] of heads x 64: interleaved-pair RoPE on the first rope_heads heads of q and
+ *                 k (0 = all) at position m % seq_len, q times q_scale (0 = 1), to q, k, v [M/seq_len, heads,
+ *                 seq_len, 64] (operand)
+ *   8 GELU_ERF_OP as 3 (operand)    9 RESID16 as 4 with C and resid in the operand dtype    10 STORE16 as 0 (operand)
+ * acc = [A[:, :k_split] | A2[:, :K - k_split]] . W^T when A2 is set (both [M,K], row stride K), else A . W^T.
+ * "(operand)": the kernel stores the operand dtype. C is [M + dual_rows, N]. live_len [M / live_seq] with live_seq:
+ * the pad-row skip of an in-place RESID / RESID16 with rowkeep (row tiles without a live row are not computed).
+ * rope_out [seq_len, 32, 2] or NULL: receives the (cos, sin) table the kernel read. K % 64 == 0. */
+typedef struct f5h_op_gemm_args {
+  int32_t compute, epi, M, N, K, k_split;
+  const float* A;
+  const float* A2;
+  const float* W;        /* [N,K] */
+  const float* bias;     /* [N] or NULL */
+  float* C;
+  const float* resid;    /* [M,N] or NULL */
+  const float* gate;     /* [N] or NULL (= 1) */
+  const uint8_t* rowkeep;/* [M] or NULL (= 1) */
+  const int32_t* live_len;
+  int32_t live_seq;
+  int32_t seq_len, heads, rope_heads;
+  float q_scale;
+  const float* add;      /* [M + dual_rows, ld_add] */
+  int64_t ld_add;
+  int64_t dual_rows;
+  float* q;
+  float* k;
+  float* v;
+  float* rope_out;
+} f5h_op_gemm_args;
+int f5h_op_gemm_epi(void* stream, const f5h_op_gemm_args* args, void* workspace, size_t workspace_bytes);
 
 /* Tuning/test hook: pin the 16-bit GEMM tile configuration for all later launches in this
  * process (0, 1, 5, 11, 12, 13), or -1 to restore the automatic per-shape choice. */

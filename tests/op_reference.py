@@ -1,0 +1,229 @@
+"""References for the op-level parity tests (tests/test_gpu_ops.py, tests/test_op_refs.py): plain torch
+implementations of the operations behind the conv, norm and GEMM-epilogue kernels, written from the model
+definitions (modules.py line numbers below are the reference model's; x_transformers for RMSNorm and the rotary
+embedding), not from the kernels. Every function takes `dtype`: torch.float64 gives the reference R64,
+torch.float32 the same formula in single precision, R32, whose distance from R64 is the yardstick of the
+tolerance (`excess_ratio`). `variant` selects a deliberately wrong form (WRONG_* below): tests/test_op_refs.py
+requires each of them to fail the tolerance on the inputs the GPU tests use.
+
+Inputs are the values the kernel reads: what a kernel reads in the operand dtype is rounded by the caller first
+(`rnd`). The references never round; the rounding of a stored 16-bit output is the `u_out` term of the tolerance.
+"""
+
+from __future__ import annotations
+
+import math
+
+import torch
+import torch.nn.functional as F
+
+OP_DTYPE = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
+# unit roundoff of a stored output (round to nearest): half an ulp relative to the value
+U_OUT = {"fp32": 0.0, "bf16": 2.0 ** -8, "fp16": 2.0 ** -11}
+ACC_FACTOR = 8.0  # accumulation-order allowance on max|R32 - R64| (MFMA k-slabs, wave reductions)
+
+
+def rnd(t, compute):
+    """The fp32 values of t after rounding to compute's operand dtype (what a kernel reads from a 16-bit buffer)."""
+    return None if t is None else t.to(OP_DTYPE[compute]).float()
+
+
+def excess_ratio(out, r64, r32, u_out, extra=None):
+    """max(|out - R64| - u_out |R64| - extra) / max|R32 - R64|: the elementwise tolerance |out - R64| <= u_out |R64|
+    + extra + ACC_FACTOR max|R32 - R64| holds iff this is <= ACC_FACTOR. `extra`: an elementwise allowance derived
+    next to the case that uses it (None: 0). A non-finite `out` gives inf; when R32 == R64 exactly (all-zero
+    outputs) any positive excess gives inf."""
+    out, r64 = out.double(), r64.double()
+    if not bool(torch.isfinite(out).all()):
+        return math.inf
+    acc = float((r32.double() - r64).abs().max())
+    exc = (out - r64).abs() - u_out * r64.abs()
+    if extra is not None:
+        exc = exc - extra.double()
+    exc = float(exc.max())
+    if acc == 0.0:
+        return 0.0 if exc <= 0.0 else math.inf
+    return exc / acc
+
+
+def assert_close(out, r64, r32, u_out, what, factor=ACC_FACTOR, extra=None):
+    """Assert the tolerance; `what` = "op/compute/case". Prints the measured ratio before asserting (pytest -s:
+    the table in tests/test_gpu_ops.py is the worst of these lines per op and compute mode)."""
+    ratio = excess_ratio(out, r64, r32, u_out, extra)
+    acc = float((r32.double() - r64.double()).abs().max())
+    print(f"[op-parity] {what}: ratio {ratio:.3f} (max|R32-R64| {acc:.3e})")
+    assert ratio <= factor, (f"{what}: max(|out - R64| - u_out|R64|) / max|R32 - R64| = {ratio:.4g} > {factor} "
+                             f"(max|R32 - R64| = {acc:.3e}, u_out = {u_out:.3e})")
+    return ratio
+
+
+# ---------------------------------------------------------------- ConvPositionEmbedding layer (modules.py:175-201)
+WRONG_CONV = ("taps30", "shifted_centre", "keep_ignored_on_input", "halo_from_neighbour", "no_masked_row_zero")
+
+
+def conv_pos(x, w, bias, keep=None, resid=None, dtype=torch.float64, variant=None):
+    """y = mish(where(keep, conv(where(keep, x, 0)) + bias, 0)) [+ resid]: Conv1d(d, d, 31, groups=16, padding=15)
+    over time per sequence (modules.py:180), the mask on its input and output (:193, :197), nn.Mish (:181).
+    x [S,L,d], w [d, d/16, 31], keep [S,L] bool or None, resid [S,L,d] or None."""
+    S, L, d = x.shape
+    xx, w, bias = x.to(dtype), w.to(dtype), bias.to(dtype)
+    k3 = None if keep is None else keep.bool()[..., None]
+    if k3 is not None and variant != "keep_ignored_on_input":
+        xx = torch.where(k3, xx, torch.zeros((), dtype=dtype))
+    xt = xx.transpose(1, 2)  # [S, d, L]
+    if variant == "halo_from_neighbour":  # one long sequence: the 15-row halo crosses the sequence seams
+        xt = xx.reshape(1, S * L, d).transpose(1, 2)
+    if variant == "taps30":
+        y = F.conv1d(xt, w[..., :30], bias, padding=15, groups=16)[..., :xt.shape[-1]]
+    elif variant == "shifted_centre":
+        y = F.conv1d(F.pad(xt, (16, 14)), w, bias, groups=16)
+    else:
+        y = F.conv1d(xt, w, bias, padding=15, groups=16)
+    y = y.transpose(1, 2).reshape(S, L, d)
+    if k3 is not None and variant != "no_masked_row_zero":
+        y = torch.where(k3, y, torch.zeros((), dtype=dtype))
+    y = F.mish(y)
+    return y if resid is None else y + resid.to(dtype)
+
+
+# ---------------------------------------------------------------- row norms
+WRONG_LN = ("eps_1e-5", "unbiased_variance")
+WRONG_RMS = ("no_sqrt_d",)
+
+
+def _layer_norm(x, eps, variant):
+    mean = x.mean(-1, keepdim=True)
+    var = x.var(-1, keepdim=True, unbiased=(variant == "unbiased_variance"))
+    return (x - mean) / torch.sqrt(var + (1e-5 if variant == "eps_1e-5" else eps))
+
+
+def ln_modulate(h, shift, scale, dtype=torch.float64, variant=None):
+    """AdaLayerNorm / AdaLayerNorm_Final (modules.py:319, 325, 340, 346): LayerNorm(d, no affine, eps 1e-6)(h) *
+    (1 + scale) + shift. h [M,d]; shift, scale [d]."""
+    return _layer_norm(h.to(dtype), 1e-6, variant) * (1 + scale.to(dtype)) + shift.to(dtype)
+
+
+def rms_norm(h, g, dtype=torch.float64, variant=None):
+    """x_transformers RMSNorm: F.normalize(x, dim=-1) * dim ** 0.5 * g, F.normalize dividing by max(|x|_2, 1e-12)."""
+    h = h.to(dtype)
+    n = h / h.norm(dim=-1, keepdim=True).clamp_min(1e-12)
+    return n * g.to(dtype) * (1.0 if variant == "no_sqrt_d" else h.shape[-1] ** 0.5)
+
+
+def dwconv_ln(x, dw_w, dw_b, ln_w, ln_b, dtype=torch.float64, variant=None):
+    """ConvNeXtV2Block front half (modules.py:261-264, 272-275): depthwise Conv1d(C, C, 7, padding=3, groups=C) over
+    time, then LayerNorm(C, eps 1e-6) with affine. x [S,L,C], dw_w [C,7]."""
+    C = x.shape[-1]
+    y = F.conv1d(x.to(dtype).transpose(1, 2), dw_w.to(dtype)[:, None, :], dw_b.to(dtype), padding=3, groups=C)
+    return _layer_norm(y.transpose(1, 2), 1e-6, variant) * ln_w.to(dtype) + ln_b.to(dtype)
+
+
+WRONG_GRN = ("norm_over_channels",)
+
+
+def grn(x, gamma, beta, dtype=torch.float64, variant=None):
+    """GRN (modules.py:242-245): Gx = |x|_2 over time (dim 1), Nx = Gx / (mean over channels of Gx + 1e-6),
+    gamma (x Nx) + beta + x. x [S,L,C]."""
+    x = x.to(dtype)
+    if variant == "norm_over_channels":
+        Gx = torch.norm(x, p=2, dim=2, keepdim=True)
+        Nx = Gx / (Gx.mean(dim=1, keepdim=True) + 1e-6)
+    else:
+        Gx = torch.norm(x, p=2, dim=1, keepdim=True)
+        Nx = Gx / (Gx.mean(dim=-1, keepdim=True) + 1e-6)
+    return gamma.to(dtype) * (x * Nx) + beta.to(dtype) + x
+
+
+# ---------------------------------------------------------------- GEMM epilogues
+WRONG_GEMM = {"gelu_tanh": ("gelu_erf_for_tanh",), "resid": ("gate_on_residual",), "resid16": ("gate_on_residual",),
+              "resid_fill": ("fill_keeps_c",), "qkv": ("rope_half_split", "rope_on_every_head", "q_unscaled")}
+
+
+def rope_table(L, dtype=torch.float64):
+    """x_transformers RotaryEmbedding(64): inv_freq_j = 10000^(-2j/64), (cos, sin)(n inv_freq_j), [L,32,2]."""
+    inv = 1.0 / (10000.0 ** (torch.arange(0, 64, 2, dtype=dtype) / 64.0))
+    f = torch.arange(L, dtype=dtype)[:, None] * inv[None, :]
+    return torch.stack((torch.cos(f), torch.sin(f)), dim=-1)
+
+
+def _rope(t, cos, sin, variant):
+    """x_transformers apply_rotary_pos_emb with rotate_half on interleaved pairs (x_{2i}, x_{2i+1}): t cos +
+    rotate_half(t) sin, the pair's frequency repeated. t [S,L,H,64]; cos, sin [L,32]."""
+    c, s = cos[None, :, None, :], sin[None, :, None, :]
+    if variant == "rope_half_split":  # pairs (x_i, x_{i+32}) instead
+        a, b = t[..., :32], t[..., 32:]
+        return torch.cat((a * c - b * s, b * c + a * s), dim=-1)
+    a, b = t[..., 0::2], t[..., 1::2]
+    return torch.stack((a * c - b * s, b * c + a * s), dim=-1).flatten(-2)
+
+
+def gemm_epi(epi, A, W, bias=None, C=None, resid=None, gate=None, keep=None, add=None, dual_rows=0, seq_len=0,
+             heads=0, rope_heads=0, q_scale=0.0, rope=None, dtype=torch.float64, variant=None):
+    """acc = A W^T + bias, then the epilogue (kernels.h `Epi`; the model lines they stand for):
+    store / store16: acc. silu: SiLU (modules.py:857). gelu_tanh: nn.GELU(approximate="tanh") (:358). gelu_erf /
+    gelu_erf_op: nn.GELU() (:266). resid / resid16: x + gate * masked_fill(sub-layer output, ~mask, 0)
+    (:551-554, 755-757): where(keep, R + gate acc, R), R = resid if given else C. resid_fill: residual + x then
+    masked_fill(~mask, 0) of the ConvNeXt text blocks: where(keep, C + acc, 0). inproj: the split input projection,
+    C[m] = acc + add[m] and, with dual_rows, C[m + dual_rows] = acc + add[m + dual_rows]. qkv: to_q / to_k / to_v
+    columns [q | k | v], heads of 64; rotary embedding on the first rope_heads heads (0: all) of q and k at position
+    m % seq_len from `rope` [L,32,2] (cos, sin), q times q_scale (0: unscaled); returns q, k, v [S,H,L,64]."""
+    acc = A.to(dtype) @ W.to(dtype).t()
+    if bias is not None:
+        acc = acc + bias.to(dtype)
+    M, N = acc.shape
+    kp = None if keep is None else keep.bool()[:, None]
+    if epi in ("store", "store16"):
+        return acc
+    if epi == "silu":
+        return F.silu(acc)
+    if epi == "gelu_tanh":
+        return F.gelu(acc) if variant == "gelu_erf_for_tanh" else F.gelu(acc, approximate="tanh")
+    if epi in ("gelu_erf", "gelu_erf_op"):
+        return F.gelu(acc)
+    if epi in ("resid", "resid16"):
+        R = (C if resid is None else resid).to(dtype)
+        gt = torch.ones(N, dtype=dtype) if gate is None else gate.to(dtype)
+        upd = gt * (R + acc) if variant == "gate_on_residual" else R + gt * acc
+        return upd if kp is None else torch.where(kp, upd, R)
+    if epi == "resid_fill":
+        Cd = C.to(dtype)
+        upd = Cd + acc
+        if kp is None:
+            return upd
+        return torch.where(kp, upd, Cd if variant == "fill_keeps_c" else torch.zeros((), dtype=dtype))
+    if epi == "inproj":
+        ad = add.to(dtype)
+        out = acc + ad[:M, :N]
+        return out if not dual_rows else torch.cat((out, torch.full((dual_rows - M, N), float("nan"), dtype=dtype),
+                                                    acc + ad[dual_rows:dual_rows + M, :N]))
+    assert epi == "qkv"
+    S, inner = M // seq_len, heads * 64
+    q, k, v = (acc[:, i * inner:(i + 1) * inner].reshape(S, seq_len, heads, 64) for i in range(3))
+    cos, sin = rope[..., 0].to(dtype), rope[..., 1].to(dtype)
+    nrope = heads if (rope_heads == 0 or variant == "rope_on_every_head") else rope_heads
+    q = torch.cat((_rope(q[:, :, :nrope], cos, sin, variant), q[:, :, nrope:]), dim=2)
+    k = torch.cat((_rope(k[:, :, :nrope], cos, sin, variant), k[:, :, nrope:]), dim=2)
+    if q_scale != 0.0 and variant != "q_unscaled":
+        q = q * q_scale
+    return tuple(t.permute(0, 2, 1, 3).contiguous() for t in (q, k, v))
+
+
+# ---------------------------------------------------------------- attention
+def attention(Q, K, V, kv_len=None, dtype=torch.float64, log2_scores=False):
+    """softmax(Q K^T / sqrt(64) + key mask) V, [S,H,N,64] -> [S,N,H*64] (F.scaled_dot_product_attention in the
+    AttnProcessor, modules.py:470-555). log2_scores: Q already carries log2(e) / sqrt(64) (the engine's layout), so
+    the softmax is 2^s / sum 2^s of s = Q K^T. Returns (O, sqrt(P^2 . V^2), sqrt(sum_k P^2)): the last two are the
+    scales of the error that rounding the probabilities P leaves in the numerator and in the row sum."""
+    S, H, N, _ = Q.shape
+    sc = Q.to(dtype) @ K.to(dtype).transpose(-1, -2)
+    if not log2_scores:
+        sc = sc / 8.0
+    if kv_len is not None:
+        dead = torch.arange(N)[None, :] >= kv_len.long()[:, None]
+        sc = sc.masked_fill(dead[:, None, None, :], float("-inf"))
+    p = torch.exp2(sc - sc.amax(-1, keepdim=True)) if log2_scores else torch.softmax(sc, dim=-1)
+    p = p / p.sum(-1, keepdim=True)
+    Vd = V.to(dtype)
+    fold = lambda t: t.transpose(1, 2).reshape(S, N, H * 64)  # noqa: E731
+    return (fold(p @ Vd), fold(torch.sqrt(p.square() @ Vd.square())),
+            fold(torch.sqrt(p.square().sum(-1, keepdim=True)).expand(S, H, N, 64)))
