@@ -124,7 +124,8 @@ hipError_t step_advance(int* kstep, int* tick, hipStream_t st) {
 // (kernels.h LnFoldArgs). u_s[n] = sum_k (1 + scale_s[k]) W[n][k] and v_s[n] = sum_k shift_s[k] W[n][k], for the
 // 16 steps of a step group: a [16 steps x d] . [d x 64 columns] product per wave, on the matrix pipes. The fp32
 // (1 + scale) and shift rows enter as two 16-bit parts each (hi = the rounded value, lo = the rounded remainder:
-// ~2^-16 relative to the value with bf16, ~2^-22 with fp16) accumulated into the same fp32 sums; W in its own 16-bit
+// ~2^-16 relative to the value with bf16, ~2^-22 with fp16, whose lo part is subnormal for |x| below ~0.125 and is
+// kept by the conversion and the MFMA, down to fp16's absolute spacing 2^-24: tests/test_gpu_fold_ops.py) accumulated into the same fp32 sums; W in its own 16-bit
 // type. Wave = (step group, 64 output columns of W1 or Wqkv, layer): four 16x16 column tiles, u and v, so every W
 // element is read once per step group (230 MB at C2: the kernel's floor is that read). Operands straight from
 // global memory (a lane's 16 B of a W row and 32 B of each table row per 32 k), two K steps' loads in flight.

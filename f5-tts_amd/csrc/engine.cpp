@@ -2369,6 +2369,37 @@ int f5h_op_gemm_epi(void* stream, const f5h_op_gemm_args* a, void* workspace, si
   } else if (!a->C) {
     return fail(F5H_EINVAL, "op_gemm_epi: null C");
   }
+  // LayerNorm / RMSNorm fold forms: launch_t's contract (gemm_impl.h), refused here with a message
+  const bool fold_prod = a->ln_part_out != nullptr, fold_cons = a->ln_part_in != nullptr;
+  const bool fold = fold_prod || fold_cons || a->hs_scale || a->hs_out || a->ln_u || a->ln_v || a->ln_rms || a->ln_nparts;
+  if (fold) {
+    if (!compute) return fail(F5H_EINVAL, "op_gemm_epi: the fold forms need a 16-bit compute mode");
+    if (fold_prod && fold_cons)
+      return fail(F5H_EINVAL, "op_gemm_epi: fold producer (ln_part_out) and consumer (ln_part_in) fields together");
+    if (!fold_prod && !fold_cons)
+      return fail(F5H_EINVAL, "op_gemm_epi: fold fields without ln_part_out or ln_part_in");
+    if (a->ln_rms != 0 && a->ln_rms != 1) return fail(F5H_EINVAL, "op_gemm_epi: ln_rms must be 0 or 1");
+    if (a->ln_nparts < 1 || a->ln_nparts > 16)
+      return fail(F5H_EINVAL, "op_gemm_epi: ln_nparts must be 1..16");
+    if (N % 128) return fail(F5H_EINVAL, "op_gemm_epi: the fold forms need N % 128 == 0");
+    if (a->live_len) return fail(F5H_EINVAL, "op_gemm_epi: the fold forms take no live_len");
+    if (a->rowkeep && !a->ln_rms) return fail(F5H_EINVAL, "op_gemm_epi: rowkeep only with the ln_rms fold form");
+    if (a->A2) return fail(F5H_EINVAL, "op_gemm_epi: the fold forms take no A2");
+    if (fold_prod) {
+      if (epi != EPI_RESID16) return fail(F5H_EINVAL, "op_gemm_epi: the fold producer is EPI_RESID16");
+      if (a->ln_nparts != N / 64) return fail(F5H_EINVAL, "op_gemm_epi: producer ln_nparts must be N / 64");
+      if (a->ln_u || a->ln_v) return fail(F5H_EINVAL, "op_gemm_epi: ln_u / ln_v go with the fold consumer");
+      if (a->ln_rms ? (a->hs_scale || a->hs_out) : (!a->hs_scale || !a->hs_out))
+        return fail(F5H_EINVAL, "op_gemm_epi: the LayerNorm producer needs hs_scale and hs_out, the ln_rms form neither");
+    } else {
+      if (epi != EPI_GELU_TANH && epi != EPI_QKV)
+        return fail(F5H_EINVAL, "op_gemm_epi: the fold consumer is EPI_GELU_TANH or EPI_QKV");
+      if (a->ln_nparts != K / 64) return fail(F5H_EINVAL, "op_gemm_epi: consumer ln_nparts must be K / 64");
+      if (a->hs_scale || a->hs_out) return fail(F5H_EINVAL, "op_gemm_epi: hs_scale / hs_out go with the fold producer");
+      if (a->ln_rms ? (a->ln_u || a->ln_v) : (!a->ln_u || !a->ln_v))
+        return fail(F5H_EINVAL, "op_gemm_epi: the LayerNorm consumer needs ln_u and ln_v, the ln_rms form neither");
+    }
+  }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const size_t es = compute ? 2 : 4;
   const int Npad = (N + 127) / 128 * 128;
@@ -2381,6 +2412,10 @@ int f5h_op_gemm_epi(void* stream, const f5h_op_gemm_args* a, void* workspace, si
   void* a2op = (compute && a->A2) ? ws.take((size_t)nA * es) : nullptr;
   void* cop = (compute && out_op) ? ws.take((size_t)nC * es) : nullptr;
   void* rop = (compute && epi == EPI_RESID16 && a->resid) ? ws.take((size_t)nC * es) : nullptr;
+  // fold producer outputs, each with F5H_OP_GUARD_ROWS rows past M that the launch must leave alone
+  const size_t hs_live = (size_t)M * N * 2, hs_all = (size_t)(M + F5H_OP_GUARD_ROWS) * N * 2;
+  const size_t lp_live = (size_t)M * a->ln_nparts * 8, lp_all = (size_t)(M + F5H_OP_GUARD_ROWS) * a->ln_nparts * 8;
+  void* hsop = a->hs_out ? ws.take(hs_all) : nullptr;
   void *qop = nullptr, *kop = nullptr, *vop = nullptr;
   float2* rope = nullptr;
   if (epi == EPI_QKV) {
@@ -2447,13 +2482,94 @@ int f5h_op_gemm_epi(void* stream, const f5h_op_gemm_args* a, void* workspace, si
     g.C = nullptr;
     g.ldc = 0;
   }
+  if (fold_prod) {
+    // 0xFF bytes: NaN in fp32 and in both 16-bit types. Live rows: NaN with poison, else 0; guard rows: NaN
+    const int live_fill = a->poison ? 0xFF : 0;
+    HIPCK(hipMemsetAsync(a->ln_part_out, live_fill, lp_live, st));
+    HIPCK(hipMemsetAsync(reinterpret_cast<char*>(a->ln_part_out) + lp_live, 0xFF, lp_all - lp_live, st));
+    g.ln_part = a->ln_part_out;
+    if (hsop) {
+      HIPCK(hipMemsetAsync(hsop, live_fill, hs_live, st));
+      HIPCK(hipMemsetAsync(reinterpret_cast<char*>(hsop) + hs_live, 0xFF, hs_all - hs_live, st));
+      g.hs = hsop;
+      g.hs_scale = a->hs_scale;
+    }
+  }
+  if (fold_cons) {
+    g.ln_part_in = a->ln_part_in;
+    g.ln_u = a->ln_u;
+    g.ln_v = a->ln_v;
+  }
+  if (fold) {
+    g.ln_nparts = a->ln_nparts;
+    g.ln_rms = a->ln_rms;
+    g.ln_eps = a->ln_eps;
+  }
   HIPCK(gemm(compute, epi, g, st));
+  if (hsop) HIPCK(op_to_f32(compute, hsop, (int64_t)(M + F5H_OP_GUARD_ROWS) * N, a->hs_out, st));
   if (cop) HIPCK(op_to_f32(compute, cop, nC, a->C, st));
   if (epi == EPI_QKV && compute) {
     HIPCK(op_to_f32(compute, qop, nqkv, a->q, st));
     HIPCK(op_to_f32(compute, kop, nqkv, a->k, st));
     HIPCK(op_to_f32(compute, vop, nqkv, a->v, st));
   }
+  return 0;
+}
+
+int f5h_op_lnfold_uv(void* stream, int32_t compute, int32_t nfe, int32_t depth, int32_t d, int32_t F, float* table,
+                     int64_t stride, int64_t out_off, const float* W1, const float* Wqkv, void* workspace,
+                     size_t workspace_bytes) {
+  if (compute != F5H_BF16 && compute != F5H_FP16) return fail(F5H_EINVAL, "op_lnfold_uv needs a 16-bit compute mode");
+  if (nfe <= 0 || depth <= 0 || d <= 0 || F <= 0 || d % 64 || F % 64)
+    return fail(F5H_EINVAL, "op_lnfold_uv needs nfe, depth > 0 and d % 64 == 0, F % 64 == 0");
+  const int64_t LW = 2 * (int64_t)F + 6 * (int64_t)d;
+  if (stride % 4 || out_off < 6 * (int64_t)d * depth || stride < out_off + depth * LW)
+    return fail(F5H_EINVAL, "op_lnfold_uv: stride % 4 == 0, u / v blocks past the modulation rows and inside the row");
+  if (!table || !W1 || !Wqkv) return fail(F5H_EINVAL, "op_lnfold_uv: null tensor");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t n1 = (int64_t)F * d, nq = 3 * (int64_t)d * d;
+  OpWs ws(workspace, workspace_bytes);
+  void* w1op = ws.take((size_t)depth * n1 * 2);
+  void* wqop = ws.take((size_t)depth * nq * 2);
+  const void** ptrs = reinterpret_cast<const void**>(ws.take(2 * (size_t)depth * sizeof(void*)));
+  OPWS_CHECK(ws, "op_lnfold_uv");
+  HIPCK(f32_to_op(compute, W1, depth * n1, w1op, st));
+  HIPCK(f32_to_op(compute, Wqkv, depth * nq, wqop, st));
+  std::vector<const void*> host(2 * (size_t)depth);
+  for (int l = 0; l < depth; ++l) {
+    host[l] = reinterpret_cast<const char*>(w1op) + (size_t)l * n1 * 2;
+    host[depth + l] = reinterpret_cast<const char*>(wqop) + (size_t)l * nq * 2;
+  }
+  HIPCK(hipMemcpyAsync(ptrs, host.data(), host.size() * sizeof(void*), hipMemcpyHostToDevice, st));
+  HIPCK(hipStreamSynchronize(st));  // `host` leaves scope
+  LnFoldArgs la{};
+  la.table = table;
+  la.stride = stride;
+  la.out_off = out_off;
+  la.nfe = nfe;
+  la.depth = depth;
+  la.d = d;
+  la.F = F;
+  la.w1 = ptrs;
+  la.wqkv = ptrs + depth;
+  HIPCK(lnfold_uv(compute, la, st));
+  return 0;
+}
+
+int f5h_op_scale_cols(void* stream, int32_t compute, int64_t rows, int32_t K, const float* W, const float* g,
+                      float* out, void* workspace, size_t workspace_bytes) {
+  if (compute != F5H_BF16 && compute != F5H_FP16) return fail(F5H_EINVAL, "op_scale_cols needs a 16-bit compute mode");
+  if (rows <= 0 || K <= 0 || K % 8) return fail(F5H_EINVAL, "op_scale_cols needs rows > 0 and K % 8 == 0");
+  if (!W || !g || !out) return fail(F5H_EINVAL, "op_scale_cols: null tensor");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t n = rows * K;
+  OpWs ws(workspace, workspace_bytes);
+  void* wop = ws.take((size_t)n * 2);
+  void* oop = ws.take((size_t)n * 2);
+  OPWS_CHECK(ws, "op_scale_cols");
+  HIPCK(f32_to_op(compute, W, n, wop, st));
+  HIPCK(scale_cols(compute, wop, rows, K, g, oop, st));
+  HIPCK(op_to_f32(compute, oop, n, out, st));
   return 0;
 }
 

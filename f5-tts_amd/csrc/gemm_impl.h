@@ -340,7 +340,7 @@ F5H_DEV float sum8_order(const float (&a)[8]) {
 // access — so the kernels' counted waits see a constant number of loads), and after the K loop combines them
 // exactly as the per-chunk-row form does (lane c of the row's 8 held partials c and c + 8) into (mean, rstd):
 // every strip holds 64 columns, so mean = the mean of the strip means, M2 = sum of the strips' M2 + 64 sum of
-// (strip mean - mean)^2 (partials past ln_nparts weigh 0).
+// (strip mean - mean)^2 (slots past ln_nparts, the next row's partials, are selected away).
 F5H_DEV void ln_row_fetch(const GemmArgs& g, int m0, int tid, int BM, u32x4 (&raw)[8]) {
   const bool on = g.ln_part_in != nullptr;
   const __amdgpu_buffer_rsrc_t st = rsrc_of(g.ln_part_in, on ? (uint64_t)g.M * g.ln_nparts * 8 : 0);
@@ -354,18 +354,17 @@ F5H_DEV void ln_row_stats(const GemmArgs& g, const u32x4 (&raw)[8], float* out) 
   const float inv_np = 1.f / (float)np;
   auto mp = [&](int p) { return __uint_as_float(raw[p >> 1][(p & 1) * 2]); };
   auto qp = [&](int p) { return __uint_as_float(raw[p >> 1][(p & 1) * 2 + 1]); };
+  // The 128-byte fetch runs past the row's own np partials into the next row's when np < 16: those slots are
+  // selected away, not multiplied by a 0 weight (0 x NaN = NaN would carry a non-finite partial of row r + 1 into
+  // row r). Finite inputs give the same bits as the weighted form: 1 x = x, and the 0 of a dropped slot adds nothing.
   float a[8], e[8];
 #pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const float w0 = c < np ? 1.f : 0.f, w1 = c + 8 < np ? 1.f : 0.f;
-    a[c] = add_nc(w0 * mp(c), w1 * mp(c + 8));
-  }
+  for (int c = 0; c < 8; ++c) a[c] = add_nc(c < np ? mp(c) : 0.f, c + 8 < np ? mp(c + 8) : 0.f);
   const float mean = mul_nc(sum8_order(a), inv_np);
 #pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const float w0 = c < np ? 1.f : 0.f, w1 = c + 8 < np ? 1.f : 0.f;
-    e[c] = add_nc(w0 * ln_m2_term(qp(c), mp(c), mean), w1 * ln_m2_term(qp(c + 8), mp(c + 8), mean));
-  }
+  for (int c = 0; c < 8; ++c)
+    e[c] = add_nc(c < np ? ln_m2_term(qp(c), mp(c), mean) : 0.f,
+                  c + 8 < np ? ln_m2_term(qp(c + 8), mp(c + 8), mean) : 0.f);
   out[0] = mean;
   out[1] = ln_rstd(sum8_order(e), inv_np, g.ln_eps);
 }

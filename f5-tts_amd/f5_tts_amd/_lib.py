@@ -59,6 +59,8 @@ EXPORTS = (
     "f5h_op_dwconv_ln",
     "f5h_op_grn",
     "f5h_op_gemm_epi",
+    "f5h_op_lnfold_uv",
+    "f5h_op_scale_cols",
     "f5h_gemm_force_config",
     "f5h_attn_force_safe",
     "f5h_debug_tile_live",
@@ -133,7 +135,15 @@ class OpGemmArgs(ctypes.Structure):
         ("q_scale", ctypes.c_float),
         ("add", ctypes.c_void_p), ("ld_add", ctypes.c_int64), ("dual_rows", ctypes.c_int64),
         ("q", ctypes.c_void_p), ("k", ctypes.c_void_p), ("v", ctypes.c_void_p), ("rope_out", ctypes.c_void_p),
+        # LayerNorm / RMSNorm fold forms (all zero: none)
+        ("hs_scale", ctypes.c_void_p), ("hs_out", ctypes.c_void_p), ("ln_part_out", ctypes.c_void_p),
+        ("ln_part_in", ctypes.c_void_p), ("ln_u", ctypes.c_void_p), ("ln_v", ctypes.c_void_p),
+        ("ln_nparts", ctypes.c_int32), ("ln_rms", ctypes.c_int32), ("ln_eps", ctypes.c_float),
+        ("poison", ctypes.c_int32),
     ]
+
+
+OP_GUARD_ROWS = 4  # F5H_OP_GUARD_ROWS
 
 
 _lib = None
@@ -213,6 +223,11 @@ def lib():
         L.f5h_op_grn.restype = ctypes.c_int
         L.f5h_op_gemm_epi.argtypes = [vp, ctypes.POINTER(OpGemmArgs), vp, sz]
         L.f5h_op_gemm_epi.restype = ctypes.c_int
+        if hasattr(L, "f5h_op_lnfold_uv"):  # (a build with the op hooks but without the fold's)
+            L.f5h_op_lnfold_uv.argtypes = [vp, i32, i32, i32, i32, i32, vp, i64, i64, vp, vp, vp, sz]
+            L.f5h_op_lnfold_uv.restype = ctypes.c_int
+            L.f5h_op_scale_cols.argtypes = [vp, i32, i64, i32, vp, vp, vp, vp, sz]
+            L.f5h_op_scale_cols.restype = ctypes.c_int
     L.f5h_gemm_force_config.argtypes = [i32]
     L.f5h_gemm_force_config.restype = ctypes.c_int
     # test hooks: bound when present, so an older build loaded through F5H_LIB (one-box A/Bs) still loads

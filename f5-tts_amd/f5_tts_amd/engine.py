@@ -409,9 +409,17 @@ EPI = {"store": 0, "silu": 1, "gelu_tanh": 2, "gelu_erf": 3, "resid": 4, "resid_
 
 
 def op_gemm_epi(epi, A, W, bias=None, C=None, compute="bf16", A2=None, k_split=0, resid=None, gate=None, rowkeep=None,
-                live_len=None, live_seq=0, add=None, dual_rows=0, seq_len=0, heads=0, rope_heads=0, q_scale=0.0):
+                live_len=None, live_seq=0, add=None, dual_rows=0, seq_len=0, heads=0, rope_heads=0, q_scale=0.0,
+                hs_scale=None, ln_producer=False, ln_part_in=None, ln_u=None, ln_v=None, ln_rms=False, ln_eps=0.0,
+                ln_nparts=None, poison=False):
     """A GEMM with epilogue `epi` (a key of EPI; f5h_op_gemm_epi). The in/out epilogues update a copy of C and
-    return it; "inproj" returns C [M + dual_rows, N]; "qkv" returns (q, k, v [S,H,L,64], rope [L,32,2])."""
+    return it; "inproj" returns C [M + dual_rows, N]; "qkv" returns (q, k, v [S,H,L,64], rope [L,32,2]).
+
+    LayerNorm / RMSNorm fold forms (f5h_op_gemm_args in include/f5h.h). ln_producer ("resid16"): returns (C, hs,
+    parts) with parts [M + OP_GUARD_ROWS, N / 64, 2] the strips' (mean, M2) and hs [M + OP_GUARD_ROWS, N] =
+    round(C (1 + hs_scale)) (None with ln_rms, which writes none); the guard rows past M start as NaN, the live rows
+    too with poison. ln_part_in [M, K / 64, 2] ("gelu_tanh" / "qkv"): the consumer, with ln_u, ln_v [N] (LayerNorm
+    form) or ln_rms, and the variance epsilon ln_eps. ln_nparts overrides the strip count (validation tests)."""
     M, K = A.shape
     N = W.shape[0]
     dev = A.device
@@ -425,6 +433,21 @@ def op_gemm_epi(epi, A, W, bias=None, C=None, compute="bf16", A2=None, k_split=0
         _lib.ptr(ll), int(live_seq)
     a.add, a.ld_add, a.dual_rows = _lib.ptr(add), (0 if add is None else add.shape[1]), int(dual_rows)
     ws_bytes = ((N + 127) // 128 * 128) * K * 4 + 3 * M * K * 4 + 3 * (M + int(dual_rows)) * N * 4 + 4096
+    hs_scale, ln_part_in, ln_u, ln_v = (_f32(t, dev) for t in (hs_scale, ln_part_in, ln_u, ln_v))
+    hs = parts = None
+    if ln_producer:
+        G = _lib.OP_GUARD_ROWS
+        a.ln_nparts = N // 64 if ln_nparts is None else int(ln_nparts)
+        parts = torch.empty(M + G, max(a.ln_nparts, 1), 2, dtype=torch.float32, device=dev)
+        a.ln_part_out = parts.data_ptr()
+        if hs_scale is not None:
+            hs = torch.empty(M + G, N, dtype=torch.float32, device=dev)
+            a.hs_scale, a.hs_out = hs_scale.data_ptr(), hs.data_ptr()
+            ws_bytes += (M + G) * N * 2 + 256
+    elif ln_part_in is not None:
+        a.ln_nparts = K // 64 if ln_nparts is None else int(ln_nparts)
+        a.ln_part_in, a.ln_u, a.ln_v = ln_part_in.data_ptr(), _lib.ptr(ln_u), _lib.ptr(ln_v)
+    a.ln_rms, a.ln_eps, a.poison = int(bool(ln_rms)), float(ln_eps), int(bool(poison))
     out = None
     if epi == "qkv":
         S = M // seq_len if seq_len > 0 else 0
@@ -445,6 +468,34 @@ def op_gemm_epi(epi, A, W, bias=None, C=None, compute="bf16", A2=None, k_split=0
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     _lib.check(_lib.lib().f5h_op_gemm_epi(_lib.stream_handle(dev), ctypes.byref(a), ws.data_ptr(), ws.numel()),
                "f5h_op_gemm_epi")
+    return (out, hs, parts) if ln_producer else out
+
+
+def op_lnfold_uv(table, W1, Wqkv, nfe, out_off, compute="bf16"):
+    """lnfold_uv alone (f5h_op_lnfold_uv): table [rows >= nfe, stride] fp32 with the AdaLN modulation rows of
+    `depth` layers in its first 6 d depth columns; W1 [depth, F, d], Wqkv [depth, 3d, d]. Returns a copy of the
+    table with the u / v blocks of steps < nfe written from column out_off on."""
+    depth, F, d = W1.shape
+    dev = table.device
+    table = _f32(table).clone()
+    W1, Wqkv = _f32(W1, dev), _f32(Wqkv, dev)
+    ws = torch.empty((W1.numel() + Wqkv.numel()) * 2 + 16 * depth + 2048, dtype=torch.uint8, device=dev)
+    _lib.check(_lib.lib().f5h_op_lnfold_uv(_lib.stream_handle(dev), _lib.COMPUTE[compute], int(nfe), depth, d, F,
+                                           table.data_ptr(), table.shape[1], int(out_off), W1.data_ptr(),
+                                           Wqkv.data_ptr(), ws.data_ptr(), ws.numel()), "f5h_op_lnfold_uv")
+    return table
+
+
+def op_scale_cols(W, g, compute="bf16"):
+    """scale_cols alone (f5h_op_scale_cols): round(round(W) g[None, :]) as fp32; W [rows, K], g [K]."""
+    rows, K = W.shape
+    dev = W.device
+    W, g = _f32(W), _f32(g, dev)
+    out = torch.empty(rows, K, dtype=torch.float32, device=dev)
+    ws = torch.empty(W.numel() * 4 + 1024, dtype=torch.uint8, device=dev)
+    _lib.check(_lib.lib().f5h_op_scale_cols(_lib.stream_handle(dev), _lib.COMPUTE[compute], rows, K, W.data_ptr(),
+                                            g.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel()),
+               "f5h_op_scale_cols")
     return out
 
 

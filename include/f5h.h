@@ -334,7 +334,7 @@ int f5h_op_dwconv_ln(void* stream, int32_t compute, int32_t S, int32_t L, int32_
 int f5h_op_grn(void* stream, int32_t compute, int32_t S, int32_t L, int32_t C, const float* x, const float* gamma,
                const float* beta, float* out, void* workspace, size_t workspace_bytes);
 
-/* f5h_op_linear with any GEMM epilogue but the LayerNorm / RMSNorm fold forms. epi:
+/* f5h_op_linear with any GEMM epilogue (the LayerNorm / RMSNorm fold forms: the struct's trailing fields). epi:
  *   0 STORE       C = acc + bias                          1 SILU          C = silu(acc + bias)
  *   2 GELU_TANH   C = gelu_tanh(acc + bias)  (operand)    3 GELU_ERF      C = gelu_erf(acc + bias)
  *   4 RESID       C = keep[m] ? R + gate[n] (acc + bias) : R, R = resid or C
@@ -369,8 +369,44 @@ typedef struct f5h_op_gemm_args {
   float* k;
   float* v;
   float* rope_out;
+  /* LayerNorm / RMSNorm fold forms (16-bit modes; all zero: none). ln_nparts = the row's 64-column strips.
+   * Producer (epi 9, ln_part_out set; ln_nparts = N / 64, N % 128 == 0): besides C, the kernel writes per row and
+   * strip the (mean, M2) of the stored C into ln_part_out [M + F5H_OP_GUARD_ROWS, ln_nparts, 2] and, in the
+   * LayerNorm form (hs_scale [N] and hs_out both set), hs = round(C (1 + hs_scale)) into hs_out
+   * [M + F5H_OP_GUARD_ROWS, N] (fp32 view of the 16-bit buffer). ln_rms = 1: the RMSNorm form, strips hold
+   * (0, sum of squares), no hs (hs_scale, hs_out NULL); rowkeep is allowed in this form only. Both outputs come
+   * back with their guard rows, which the hook fills with NaN before the launch (the kernel's descriptors end at
+   * row M); with poison != 0 the live rows start as NaN too (else 0), so an unwritten strip shows.
+   * Consumer (epi 2 or 7, ln_part_in [M, ln_nparts, 2] set; ln_nparts = K / 64): x = rstd (acc - mean ln_u[n]) +
+   * ln_v[n] + bias ahead of the activation, (mean, rstd) combined from the row's partials with variance epsilon
+   * ln_eps; A is hs. LayerNorm form: ln_u, ln_v [N] both set; RMSNorm form (ln_rms = 1): both NULL. live_len and
+   * fp32 compute are refused with either form. */
+  const float* hs_scale;
+  float* hs_out;
+  float* ln_part_out;
+  const float* ln_part_in;
+  const float* ln_u;
+  const float* ln_v;
+  int32_t ln_nparts, ln_rms;
+  float ln_eps;
+  int32_t poison;
 } f5h_op_gemm_args;
+#define F5H_OP_GUARD_ROWS 4
 int f5h_op_gemm_epi(void* stream, const f5h_op_gemm_args* args, void* workspace, size_t workspace_bytes);
+/* lnfold_uv alone (16-bit modes): table [rows, stride] fp32 holds, per ODE step s < nfe, the AdaLN modulation rows
+ * of `depth` layers ([depth][6][d]: shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp) in its first
+ * 6 d depth floats; the kernel writes, per step and layer l, at column out_off + l (2F + 6d): u1 [F], v1 [F] (FFN1,
+ * mlp rows), u2 [3d], v2 [3d] (QKV, msa rows), u = sum_k (1 + sc_k) W[n,k], v = sum_k sh_k W[n,k]. W1 [depth,F,d]
+ * and Wqkv [depth,3d,d] fp32, rounded to the operand dtype on the device. The table is updated in place (rows >=
+ * nfe are the caller's guard). d % 64 == 0, F % 64 == 0, out_off >= 6 d depth, stride % 4 == 0,
+ * stride >= out_off + depth (2F + 6d). */
+int f5h_op_lnfold_uv(void* stream, int32_t compute, int32_t nfe, int32_t depth, int32_t d, int32_t F, float* table,
+                     int64_t stride, int64_t out_off, const float* W1, const float* Wqkv, void* workspace,
+                     size_t workspace_bytes);
+/* scale_cols alone (16-bit modes): out[n][k] = round(round(W[n][k]) g[k]); W, out [rows, K] fp32 views of the 16-bit
+ * buffers, g [K]. K % 8 == 0. */
+int f5h_op_scale_cols(void* stream, int32_t compute, int64_t rows, int32_t K, const float* W, const float* g,
+                      float* out, void* workspace, size_t workspace_bytes);
 
 /* Tuning/test hook: pin the 16-bit GEMM tile configuration for all later launches in this
  * process (0, 1, 5, 11, 12, 13), or -1 to restore the automatic per-shape choice. */

@@ -1,5 +1,5 @@
-"""Seeded inputs of the op-level parity tests, shared by tests/test_gpu_ops.py (the kernels against the
-references) and tests/test_op_refs.py (wrong variants of the references against the same tolerance on the same
+"""Seeded inputs of the op-level parity tests, shared by tests/test_gpu_ops.py and tests/test_gpu_fold_ops.py (the
+kernels against the references) and tests/test_op_refs.py (wrong variants of the references against the same tolerance on the same
 inputs). Shapes are the smallest that reach each launcher branch and edge; every builder returns fp32 CPU tensors
 already rounded to the compute mode's operand dtype where the kernel reads that dtype."""
 
@@ -262,3 +262,169 @@ def qkv_case(compute, H, rope_heads, q_scale, K):
 def qkv_ref(c, rope, dtype, variant=None):
     return R.gemm_epi("qkv", c["A_read"], c["W_read"], c["bias"], seq_len=QKV_L, heads=c["H"],
                       rope_heads=c["rope_heads"], q_scale=c["q_scale"], rope=rope, dtype=dtype, variant=variant)
+
+
+# ---------------------------------------------------------------- LayerNorm / RMSNorm fold
+# Strip counts np = d / 64 (the fold's partials per row): 2 = one partial or none per lane of the row's 8, 8 = exactly
+# one, 12 = one or two and the once-per-row form's 128-byte fetch runs into the next row's partials, 16 = the
+# production shape. M: 1 = a single row, 70 = ragged inside a 64 / 128 / 192-row tile, 300 = a full 256-row tile plus
+# a ragged one. Producer K (64: one k tile, 256: several) is independent of d.
+FOLD_ROW_KINDS = {1: "mean=100sigma", 2: "sigma=1e-2", 3: "constant", 4: "constant strip", 5: "strip means apart",
+                  6: "zero (rms) / ordinary"}
+FOLD_PROD_SHAPES = [(1, 128, 64), (70, 128, 256), (300, 512, 64), (70, 768, 256), (300, 768, 64), (1, 1024, 256),
+                    (70, 1024, 64), (300, 1024, 256)]                      # (M, N = d, K)
+# variant -> what reaches the kernel. The rows of FOLD_ROW_KINDS get A = 0, so their h' is R + gate bias: exactly the
+# planted row where the bias is zero (ln "inplace", rms "plain") or the row is masked (rms "keep").
+FOLD_PROD_VARIANTS = {"ln": ("gate_resid", "inplace"), "rms": ("plain", "keep")}
+
+
+def fold_rows(M, d, g, rms):
+    """h' rows [M,d] (fp32, not yet rounded): ordinary N(0,1) rows and, from row 1 on when M allows, a row with
+    mean = 100 sigma (cancellation), one with sigma = 1e-2 around mean 1 (variance near, above, the 1e-6 epsilon), a
+    constant row, a row with one constant strip, a row whose strip means lie far apart (the between-strip term of the
+    combine dominates; in the constant row it vanishes) and, for the RMSNorm form, an all-zero row."""
+    T = torch.randn(M, d, generator=g)
+    if M >= 8:
+        T[1] = 100.0 + torch.randn(d, generator=g)
+        T[2] = 1.0 + 1e-2 * torch.randn(d, generator=g)
+        T[3] = 3.0
+        T[4, 64:128] = 0.5
+        T[5] = T[5] + 8.0 * torch.randn(d // 64, generator=g).repeat_interleave(64)
+        if rms:
+            T[6] = 0.0
+    return T
+
+
+def fold_special_rows(M):
+    return list(range(1, 7)) if M >= 8 else []
+
+
+@functools.lru_cache(maxsize=None)
+def fold_prod_case(compute, form, variant, M, N, K):
+    """An EPI_RESID16 launch whose output rows h' are fold_rows: ordinary rows come from the GEMM, the special rows
+    have A = 0 and their residual carries the planted row (less gate bias, so the sum lands near it)."""
+    rms = form == "rms"
+    g = _gen(7, M, N, K, rms, len(variant))
+    T = fold_rows(M, N, g, rms)
+    A = torch.randn(M, K, generator=g)
+    sp = fold_special_rows(M)
+    A[sp] = 0.0
+    W = torch.randn(N, K, generator=g) / K ** 0.5
+    zero_bias = variant in ("inplace", "plain")
+    bias = torch.zeros(N) if zero_bias else torch.randn(N, generator=g)
+    gate = None if variant == "inplace" else torch.randn(N, generator=g)
+    R0 = T.clone()
+    if sp and gate is not None:
+        R0[sp] = T[sp] - gate * bias
+        if variant == "keep":
+            R0[[3, 6]] = T[[3, 6]]                     # masked below: the row itself is the output
+    c = dict(epi="resid16", A=A, W=W, bias=bias, A_read=R.rnd(A, compute), W_read=R.rnd(W, compute), gate=gate,
+             u_out=R.U_OUT[compute], special=sp, exact=zero_bias, rms=rms)
+    if variant in ("gate_resid", "keep"):
+        c["C"] = torch.randn(M, N, generator=g)        # overwritten: the residual comes from `resid`
+        c["resid"] = R0
+        c["resid_read"] = R.rnd(R0, compute)
+    else:
+        c["C"] = R0
+    c["C_read"] = R.rnd(c["C"], compute)
+    if variant == "keep":
+        keep = torch.rand(M, generator=g) < 0.7
+        if sp:
+            keep[[3, 6]] = False                       # the constant and the all-zero row stay exactly as planted
+            keep[[1, 2, 4, 5]] = True
+        c["keep"] = keep
+    if not rms:
+        c["hs_scale"] = 0.3 * torch.randn(N, generator=g)
+    return c
+
+
+# Consumer: (M, d) with N = 256 (one 256-column tile; two 128-column tiles), and N = 384 once: no whole 256-column
+# tile, so a forced 256x256 configuration runs the fold in the 128x128 one.
+FOLD_GELU_SHAPES = [(1, 128, 256), (70, 128, 256), (300, 512, 256), (70, 768, 256), (70, 768, 384), (300, 768, 256),
+                    (1, 1024, 256), (70, 1024, 256), (300, 1024, 256)]    # (M, d = K, N)
+# QKV: heads = 4 (N = 768 = 3 x 256), S = 2 sequences; (seq_len, d, rope_heads, q_scale)
+FOLD_QKV_H = 4
+FOLD_QKV_CASES = [(70, 128, 0, 0.0), (70, 768, 1, Q_SCALE), (150, 512, 0, Q_SCALE), (150, 768, 0, 0.0),
+                  (150, 1024, 1, Q_SCALE), (70, 1024, 0, 0.0)]
+FOLD_EPS = {"ln": 1e-6, "rms": 1e-30}   # the two epsilons the engine passes (engine.cpp fold_consumer / rms_consumer)
+
+
+@functools.lru_cache(maxsize=None)
+def fold_cons_case(compute, form, M, d, N):
+    """What a consumer reads, every tensor already representable in the type the kernel reads it in: h' rows of
+    fold_rows rounded to the operand dtype, their fp64 strip partials rounded to fp32, and for the LayerNorm form
+    hs = round(h' (1 + sc)), u and v (fp64 sums rounded to fp32); for the RMSNorm form A = h' and W' = round(W g)."""
+    rms = form == "rms"
+    g = _gen(8, M, d, N, rms)
+    hp = R.rnd(fold_rows(M, d, g, rms), compute)
+    W = R.rnd(torch.randn(N, d, generator=g) / d ** 0.5, compute)
+    bias = 2.0 * torch.randn(N, generator=g)
+    parts = R.strip_stats(hp, torch.float64, rms).float()
+    c = dict(hp=hp, parts=parts, bias=bias, eps=FOLD_EPS[form], u_out=R.U_OUT[compute], rms=rms, u=None, v=None)
+    if rms:
+        gain = 1.0 + 0.5 * torch.randn(d, generator=g)
+        c.update(A=hp, W=R.scale_cols(W, gain, compute), gain=gain, W_plain=W)
+    else:
+        sc, sh = 0.3 * torch.randn(d, generator=g), 0.1 * torch.randn(d, generator=g)
+        c.update(A=R.fold_hs(hp, sc, compute), W=W, sc=sc, sh=sh,
+                 u=((1.0 + sc.double()) * W.double()).sum(-1).float(), v=(sh.double() * W.double()).sum(-1).float())
+    return c
+
+
+def fold_gelu_ref(c, dtype, variant=None):
+    return R.fold_consumer("gelu_tanh", c["A"], c["W"], c["bias"], c["parts"], c["u"], c["v"], c["eps"], dtype=dtype,
+                           variant=variant)
+
+
+def fold_qkv_ref(c, spec, rope, dtype, variant=None):
+    L, _, rh, qs = spec
+    return R.fold_consumer("qkv", c["A"], c["W"], c["bias"], c["parts"], c["u"], c["v"], c["eps"], dtype=dtype,
+                           variant=variant, seq_len=L, heads=FOLD_QKV_H, rope_heads=rh, q_scale=qs, rope=rope)
+
+
+# lnfold_uv: (d, F, nfe), depth 2. nfe 1 / 16 / 17 / 35: below, at and past the 16-step group, and a last group whose
+# unused lanes read the clamped last row. F = 2d at the production width, 256 otherwise.
+LNFOLD_CASES = [(128, 256, 1), (128, 256, 16), (128, 256, 17), (128, 256, 35), (768, 256, 16), (768, 256, 35),
+                (1024, 2048, 17)]
+LNFOLD_DEPTH, LNFOLD_GAP, LNFOLD_TAIL = 2, 8, 12   # floats between the modulation rows and u / v, and past them
+
+
+@functools.lru_cache(maxsize=None)
+def lnfold_case(compute, d, F, nfe):
+    """The AdaLN table [nfe + 1 (a guard row), stride]: modulation rows (scales ~0.3 N(0,1), shifts ~0.1 N(0,1), the
+    last step's shifts ~1e-4 N(0,1): in fp16 the lo parts of such shifts are subnormal), then NaN in the u / v
+    blocks, out_off > the modulation rows and stride wider than the row; the gap, the tail and the guard row hold
+    finite markers that must come back untouched."""
+    g = _gen(9, d, F, nfe)
+    depth = LNFOLD_DEPTH
+    mod = torch.randn(nfe, depth, 6, d, generator=g)
+    mod[:, :, (0, 3)] *= 0.1
+    mod[:, :, (1, 4)] *= 0.3
+    mod[nfe - 1, :, (0, 3)] *= 1e-3
+    LW = 2 * F + 6 * d
+    out_off = depth * 6 * d + LNFOLD_GAP
+    stride = out_off + depth * LW + LNFOLD_TAIL
+    table = torch.randn(nfe + 1, stride, generator=g)
+    table[:nfe, :depth * 6 * d] = mod.reshape(nfe, -1)
+    table[:nfe, out_off:out_off + depth * LW] = float("nan")
+    W1 = R.rnd(torch.randn(depth, F, d, generator=g) / d ** 0.5, compute)
+    Wqkv = R.rnd(torch.randn(depth, 3 * d, d, generator=g) / d ** 0.5, compute)
+    return dict(table=table, mod=mod, W1=W1, Wqkv=Wqkv, out_off=out_off, stride=stride, LW=LW, depth=depth)
+
+
+def lnfold_blocks(c, table, d, F, nfe):
+    """The (u1, v1, u2, v2) blocks of a table, shaped as op_reference.lnfold_uv returns them."""
+    t = table[:nfe, c["out_off"]:c["out_off"] + c["depth"] * c["LW"]].reshape(nfe, c["depth"], c["LW"])
+    return t[..., :F], t[..., F:2 * F], t[..., 2 * F:2 * F + 3 * d], t[..., 2 * F + 3 * d:]
+
+
+# scale_cols: 128 x 64 = 1024 8-element groups (four whole blocks of 256 threads), 384 x 768 = 36864 groups (144
+# blocks); 130 x 72 = 1170 groups: a ragged last block, and K = 72 is a multiple of 8 only.
+SCALE_COLS_SHAPES = [(128, 64), (384, 768), (130, 72)]
+
+
+@functools.lru_cache(maxsize=None)
+def scale_cols_case(compute, rows, K):
+    g = _gen(10, rows, K)
+    W = torch.randn(rows, K, generator=g)
+    return dict(W=W, W_read=R.rnd(W, compute), g=1.0 + 0.5 * torch.randn(K, generator=g))

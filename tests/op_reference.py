@@ -1,4 +1,5 @@
-"""References for the op-level parity tests (tests/test_gpu_ops.py, tests/test_op_refs.py): plain torch
+"""References for the op-level parity tests (tests/test_gpu_ops.py, tests/test_gpu_fold_ops.py,
+tests/test_op_refs.py): plain torch
 implementations of the operations behind the conv, norm and GEMM-epilogue kernels, written from the model
 definitions (modules.py line numbers below are the reference model's; x_transformers for RMSNorm and the rotary
 embedding), not from the kernels. Every function takes `dtype`: torch.float64 gives the reference R64,
@@ -158,7 +159,7 @@ def _rope(t, cos, sin, variant):
 
 
 def gemm_epi(epi, A, W, bias=None, C=None, resid=None, gate=None, keep=None, add=None, dual_rows=0, seq_len=0,
-             heads=0, rope_heads=0, q_scale=0.0, rope=None, dtype=torch.float64, variant=None):
+             heads=0, rope_heads=0, q_scale=0.0, rope=None, dtype=torch.float64, variant=None, pre=None):
     """acc = A W^T + bias, then the epilogue (kernels.h `Epi`; the model lines they stand for):
     store / store16: acc. silu: SiLU (modules.py:857). gelu_tanh: nn.GELU(approximate="tanh") (:358). gelu_erf /
     gelu_erf_op: nn.GELU() (:266). resid / resid16: x + gate * masked_fill(sub-layer output, ~mask, 0)
@@ -166,10 +167,14 @@ def gemm_epi(epi, A, W, bias=None, C=None, resid=None, gate=None, keep=None, add
     masked_fill(~mask, 0) of the ConvNeXt text blocks: where(keep, C + acc, 0). inproj: the split input projection,
     C[m] = acc + add[m] and, with dual_rows, C[m + dual_rows] = acc + add[m + dual_rows]. qkv: to_q / to_k / to_v
     columns [q | k | v], heads of 64; rotary embedding on the first rope_heads heads (0: all) of q and k at position
-    m % seq_len from `rope` [L,32,2] (cos, sin), q times q_scale (0: unscaled); returns q, k, v [S,H,L,64]."""
-    acc = A.to(dtype) @ W.to(dtype).t()
-    if bias is not None:
-        acc = acc + bias.to(dtype)
+    m % seq_len from `rope` [L,32,2] (cos, sin), q times q_scale (0: unscaled); returns q, k, v [S,H,L,64].
+    pre [M,N]: stands for acc + bias (fold_consumer: the epilogue applied to the normalised pre-activation)."""
+    if pre is not None:
+        acc = pre.to(dtype)
+    else:
+        acc = A.to(dtype) @ W.to(dtype).t()
+        if bias is not None:
+            acc = acc + bias.to(dtype)
     M, N = acc.shape
     kp = None if keep is None else keep.bool()[:, None]
     if epi in ("store", "store16"):
@@ -227,3 +232,113 @@ def attention(Q, K, V, kv_len=None, dtype=torch.float64, log2_scores=False):
     fold = lambda t: t.transpose(1, 2).reshape(S, N, H * 64)  # noqa: E731
     return (fold(p @ Vd), fold(torch.sqrt(p.square() @ Vd.square())),
             fold(torch.sqrt(p.square().sum(-1, keepdim=True)).expand(S, H, N, 64)))
+
+
+# ---------------------------------------------------------------- LayerNorm / RMSNorm fold (DESIGN.md §3)
+# The fold replaces aop = LN(h') (1 + sc) + sh followed by aop W^T + b with algebra inside two GEMMs:
+#   producer: hs = round(h' (1 + sc)) and per 64-column strip p of every row the (mean m_p, M2 q_p) of h';
+#   consumer: mean = mean_p m_p, M2 = sum_p q_p + 64 sum_p (m_p - mean)^2, rstd = 1 / sqrt(M2 / d + eps),
+#             x = rstd (hs W^T - mean u) + v + b with u = sum_k (1 + sc_k) W[n,k], v = sum_k sh_k W[n,k].
+# RMSNorm form: strips hold (0, sum of squares), no hs, u = v = 0, W' = round(W diag(g)), eps 1e-30.
+def strip_stats(h, dtype=torch.float64, rms=False):
+    """[M,d] -> [M, d/64, 2]: (mean, M2 = sum (x - mean)^2) of each 64-column strip, two passes. rms: (0, sum x^2)."""
+    M, d = h.shape
+    x = h.to(dtype).reshape(M, d // 64, 64)
+    mean = torch.zeros(M, d // 64, dtype=dtype) if rms else x.mean(-1)
+    return torch.stack((mean, (x - mean[..., None]).square().sum(-1)), dim=-1)
+
+
+WRONG_HS = ("sc_for_one_plus_sc",)
+
+
+def fold_hs(hp, scale, compute, variant=None):
+    """The producer's hs, to the bit: one fp32 multiply of the stored h' by the fp32 (1 + scale), one rounding."""
+    f = scale.float() if variant == "sc_for_one_plus_sc" else 1.0 + scale.float()
+    return rnd(hp.float() * f, compute)
+
+
+WRONG_COMBINE_LN = ("no_between_strip_term", "stale_13th_partial", "unbiased_variance", "eps_1e-5")
+WRONG_COMBINE_RMS = ("rms_over_16_strips",)
+WRONG_CONSUMER = ("mean_u_dropped", "v_before_rstd")
+WRONG_CONSUMER_QKV = ("fold_not_on_v",)
+
+
+def fold_combine(parts, eps, dtype=torch.float64, variant=None):
+    """Strip partials [M,np,2] -> the row's (mean, rstd), [M,1] each, as DESIGN.md §3 states it."""
+    p = parts.to(dtype)
+    m, q = p[..., 0], p[..., 1]
+    M, np_ = m.shape
+    d = 64 * np_
+    mean = m.mean(-1, keepdim=True)
+    m2 = q.sum(-1, keepdim=True)
+    if variant != "no_between_strip_term":
+        m2 = m2 + 64 * (m - mean).square().sum(-1, keepdim=True)
+    if variant == "stale_13th_partial" and np_ == 12:  # the slot after the row's 12: the next row's first partial
+        sm, sq = torch.zeros(M, 1, dtype=dtype), torch.zeros(M, 1, dtype=dtype)
+        sm[:-1, 0], sq[:-1, 0] = m[1:, 0], q[1:, 0]
+        m2 = m2 + sq + 64 * (sm - mean).square()
+    div = d - 1 if variant == "unbiased_variance" else (64 * 16 if variant == "rms_over_16_strips" else d)
+    return mean, 1.0 / torch.sqrt(m2 / div + (1e-5 if variant == "eps_1e-5" else eps))
+
+
+def fold_consumer(epi, A, W, bias, parts, u, v, eps, dtype=torch.float64, variant=None, **epi_kw):
+    """The fold consumer: x = rstd (A W^T - mean u) + v + bias, then GELU-tanh ("gelu_tanh") or RoPE / q scale /
+    scatter ("qkv"; epi_kw as gemm_epi). u, v None: 0 (the RMSNorm form)."""
+    acc = A.to(dtype) @ W.to(dtype).t()
+    mean, rstd = fold_combine(parts, eps, dtype, variant)
+    ud = torch.zeros((), dtype=dtype) if u is None else u.to(dtype)
+    vd = torch.zeros((), dtype=dtype) if v is None else v.to(dtype)
+    if variant == "mean_u_dropped":
+        x = rstd * acc + vd
+    elif variant == "v_before_rstd":
+        x = rstd * (acc - mean * ud + vd)
+    else:
+        x = rstd * (acc - mean * ud) + vd
+    if variant == "fold_not_on_v":
+        n3 = acc.shape[1] // 3
+        x = torch.cat((x[:, :2 * n3], acc[:, 2 * n3:]), dim=1)
+    return gemm_epi(epi, None, None, pre=x + bias.to(dtype), dtype=dtype, **epi_kw)
+
+
+WRONG_LNFOLD_UV = ("u_from_sc", "lo_part_dropped", "msa_rows_for_ffn1")
+
+
+def lnfold_uv(mod, W1, Wqkv, dtype=torch.float64, variant=None, compute=None):
+    """mod [nfe, depth, 6, d]: a step's AdaLN rows per layer (shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp,
+    gate_mlp; modules.py:321-323). W1 [depth,F,d], Wqkv [depth,3d,d] as the kernel reads them (rounded). Returns
+    (u1, v1 [nfe,depth,F], u2, v2 [nfe,depth,3d]): u = sum_k (1 + sc_k) W[n,k], v = sum_k sh_k W[n,k], FFN1 from the
+    mlp rows and QKV from the msa rows. lo_part_dropped: (1 + sc) and sh rounded to `compute`'s operand dtype."""
+    mod = mod.to(dtype)
+    sh_ff, sc_ff = (mod[:, :, 0], mod[:, :, 1]) if variant == "msa_rows_for_ffn1" else (mod[:, :, 3], mod[:, :, 4])
+    sh_at, sc_at = mod[:, :, 0], mod[:, :, 1]
+    one = 0.0 if variant == "u_from_sc" else 1.0
+    cut = (lambda t: rnd(t.float(), compute).to(dtype)) if variant == "lo_part_dropped" else (lambda t: t)
+    mm = lambda x, w: torch.einsum("sld,lnd->sln", cut(x), w.to(dtype))  # noqa: E731
+    return mm(one + sc_ff, W1), mm(sh_ff, W1), mm(one + sc_at, Wqkv), mm(sh_at, Wqkv)
+
+
+def lnfold_uv_extra(mod, W1, Wqkv, compute):
+    """The split allowance of lnfold_uv's outputs (derived in tests/test_gpu_fold_ops.py::test_lnfold_uv), in the
+    order of lnfold_uv's results: 6 (u_op^2 / sqrt 3) sqrt(sum_k (x_k W_nk)^2), plus for fp16 the subnormal spacing of
+    the lo part 6 (2^-25 / sqrt 3) sqrt(sum_k W_nk^2)."""
+    mod = mod.double()
+    u_op = U_OUT[compute]
+    out = []
+    for x, w in ((1.0 + mod[:, :, 4], W1), (mod[:, :, 3], W1), (1.0 + mod[:, :, 1], Wqkv), (mod[:, :, 0], Wqkv)):
+        w2 = w.double().square()
+        e = 6 * u_op ** 2 / 3 ** 0.5 * torch.sqrt(torch.einsum("sld,lnd->sln", x.square(), w2))
+        if compute == "fp16":
+            e = e + 6 * 2.0 ** -25 / 3 ** 0.5 * torch.sqrt(w2.sum(-1))[None]
+        out.append(e)
+    return out
+
+
+WRONG_SCALE_COLS = ("g_by_row",)
+
+
+def scale_cols(W_read, g, compute, variant=None):
+    """round(W g[None, :]) of the rounded W, to the bit: one fp32 multiply, one rounding."""
+    gf = g.float()
+    if variant == "g_by_row":
+        return rnd(W_read.float() * gf[torch.arange(W_read.shape[0]) % gf.numel()][:, None], compute)
+    return rnd(W_read.float() * gf[None, :], compute)
