@@ -76,7 +76,10 @@ F5H_DEV void attn_block(int& qb, int& bh) {
 
 // RSM: row sums on the matrix pipe (l^T += ones . P^T, one 32x32x16 MFMA per 16-key chunk) instead of 16 packed
 // VALU adds per tile (F5H_ATTN_ROWSUM=mfma; an A/B switch, results agree to rounding)
-template <typename T, bool PRESCALED, int NW, bool RSM>
+// WT: the store policy's write-through form of the O store (AttnArgs::store_wt; a separately compiled kernel, so
+// neither form carries a switch): each wave transposes its 32 x 64 O tile through LDS so that every store
+// instruction writes whole 128-B rows (8 lanes x 16 B), through a buffer descriptor with the sc1 policy.
+template <typename T, bool PRESCALED, int NW, bool RSM, bool WT = false>
 __global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
   typedef Op16<T> OP;
   typedef typename OP::v8 v8;
@@ -451,6 +454,8 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
       dma(2, 2);
       pass(IT{});
       l_tot = row_sum();
+      // (the write-through epilogue stages O in the ring: every wave's reads of the last tile first)
+      if constexpr (WT) __syncthreads();
     }
   }
   probe_mark(a.probe, probe_t, 2);
@@ -460,6 +465,10 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
   // (lower lanes group k, upper lanes group k+1): 4 dwordx4 stores instead of 8 dwordx2
   if (!wave_dead) {
     T* O = reinterpret_cast<T*>(a.o) + (((int64_t)s_idx * L + min(qrow, L - 1)) * a.H + head) * 64;
+    // WT: the wave's staging tile, 32 rows x 128 B past the first 4 KB of the ring (the vote flags live there;
+    // all reads of the K/V tiles have retired, see above), chunk c of row r at c ^ (r & 7)
+    uint4* const stg = lds + 256 + wid * 256;
+    const int srow = lane & 31;
 #pragma unroll
     for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -472,8 +481,28 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
         auto sx = __builtin_amdgcn_permlane32_swap(a2.x, b2.x, false, false);
         auto sy = __builtin_amdgcn_permlane32_swap(a2.y, b2.y, false, false);
         const uint4 out = make_uint4(sx[0], sy[0], sx[1], sy[1]);
-        if (qrow < L) *reinterpret_cast<uint4*>(O + 32 * u + 8 * r4 + 8 * h) = out;
+        if constexpr (WT)
+          stg[srow * 8 + ((4 * u + r4 + h) ^ (srow & 7))] = out;
+        else if (qrow < L)
+          *reinterpret_cast<uint4*>(O + 32 * u + 8 * r4 + 8 * h) = out;
       }
+    if constexpr (WT) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      // the (sequence, head)'s O columns as a buffer: rows past L fall outside its extent and are dropped by the
+      // range check (the plain form's qrow < L); wave-uniform base, so the descriptor sits in scalar registers
+      const int64_t rstride = (int64_t)a.H * 64 * sizeof(T);
+      const __amdgpu_buffer_rsrc_t ors = rsrc_of(reinterpret_cast<T*>(a.o) + ((int64_t)s_idx * L * a.H + head) * 64,
+                                                 (uint64_t)(L - 1) * rstride + 64 * sizeof(T));
+      const int row0 = qb * (32 * NW) + wid_s * 32;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int r = i * 8 + (lane >> 3), c = lane & 7;
+        const uint4 w = stg[r * 8 + (c ^ (r & 7))];
+        buffer_store16<kAuxWT>(ors, (uint32_t)((row0 + r) * rstride + c * 16), __builtin_bit_cast(u32x4, w));
+      }
+    }
   }
   probe_exit(a.probe, probe_t);
 }
@@ -545,6 +574,9 @@ __global__ __launch_bounds__(64) void attn_f32_kernel(AttnArgs a) {
   probe_exit(a.probe, probe_t);
 }
 
+// the write-through O store addresses rows by a 32-bit byte offset within one (sequence, head)'s columns
+static bool attn_wt_ok(const AttnArgs& a) { return ((int64_t)a.L + 256) * a.H * 128 < ((int64_t)1 << 31); }
+
 template <typename T>
 static void launch16(const AttnArgs& a, hipStream_t st) {
   constexpr int NW = 8;  // (two 4-wave workgroups per CU measured 40.3 vs 39.6 us at C2: kept one of 8)
@@ -553,6 +585,11 @@ static void launch16(const AttnArgs& a, hipStream_t st) {
     const char* v = getenv("F5H_ATTN_ROWSUM");
     return v && !strcmp(v, "mfma");
   }();
+  // Store policy: the engine's form (prescaled q, VALU row sums) has a write-through variant
+  if (a.prescaled && !rsm && a.store_wt && attn_wt_ok(a)) {
+    hipLaunchKernelGGL((attn16_kernel<T, true, NW, false, true>), grid, dim3(64 * NW), 0, st, a);
+    return;
+  }
   if (a.prescaled) {
     if (rsm)
       hipLaunchKernelGGL((attn16_kernel<T, true, NW, true>), grid, dim3(64 * NW), 0, st, a);
@@ -566,10 +603,19 @@ static void launch16(const AttnArgs& a, hipStream_t st) {
 static int g_force_safe = 0;
 void attention_force_safe(int on) { g_force_safe = on ? 1 : 0; }
 
+int gemm_num_cus();
+// as gemm_store_wt: a single wave = one 8-wave workgroup per CU
+int attention_store_wt(int compute, const AttnArgs& a, int want) {
+  if (store_policy_forced() >= 0) want = store_policy_forced();
+  if (want == 0 || compute == F5H_C_FP32 || !a.prescaled || !attn_wt_ok(a)) return 0;
+  return want > 0 || (int64_t)((a.L + 255) / 256) * a.S * a.H <= gemm_num_cus();
+}
+
 hipError_t attention(int compute, const AttnArgs& a0, hipStream_t st) {
   if (a0.S <= 0 || a0.H <= 0 || a0.L <= 0) return hipErrorInvalidValue;
   AttnArgs a = a0;
   a.force_safe = g_force_safe;
+  if (store_policy_forced() >= 0) a.store_wt = attention_store_wt(compute, a0, store_policy_forced());
   switch (compute) {
     case F5H_C_BF16: launch16<bf16>(a, st); break;
     case F5H_C_FP16: launch16<f16>(a, st); break;

@@ -20,7 +20,6 @@
 
 namespace f5h {
 
-constexpr int kAuxWT = 16;                 // buffer-store cache policy: sc1 (write-through)
 constexpr unsigned kChainSpinLimit = 1u << 18;
 // between polls: 2 x 64 clocks (16 x 64, to take the pollers' loads out of the computing CUs' memory queues,
 // MI355X_MICROARCH.md 'polling-cost', left the computing tiles as slow and added latency to every hand-off:

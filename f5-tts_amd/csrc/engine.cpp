@@ -71,14 +71,15 @@ struct Layer {
 struct GraphKey {
   const void* ws;
   int kind;  // 0: one NFE step, 1: the call prologue (inputs staged into the workspace)
-  int B, N, nt, nfe, use_cfg, batch_mask, probe, split, pad_skip, chain, lnfold;
+  int B, N, nt, nfe, use_cfg, batch_mask, probe, split, pad_skip, chain, lnfold, store;
   int method;  // f5h_ode_method (nfe counts evaluations = table rows: steps x stages)
   uint64_t kernel_epoch;  // bumped whenever a forced GEMM config changes
   uint32_t cfg_bits;
   bool operator==(const GraphKey& o) const {
     return ws == o.ws && kind == o.kind && B == o.B && N == o.N && nt == o.nt && nfe == o.nfe && kernel_epoch == o.kernel_epoch &&
            use_cfg == o.use_cfg && batch_mask == o.batch_mask && probe == o.probe && cfg_bits == o.cfg_bits &&
-           split == o.split && pad_skip == o.pad_skip && chain == o.chain && lnfold == o.lnfold && method == o.method;
+           split == o.split && pad_skip == o.pad_skip && chain == o.chain && lnfold == o.lnfold && store == o.store &&
+           method == o.method;
   }
 };
 
@@ -139,6 +140,12 @@ struct f5h_engine {
   const void** lnf_w = nullptr;
   int64_t ada_row = 0;
   std::atomic<int64_t> n_lnfold{0};  // backbone passes enqueued with the fold
+  // Store policy of the layer's five hot launches (kernels.h gemm_store_wt; DESIGN.md §3 'Launch boundaries'):
+  // -1 = auto (write-through for the classes of kStoreAutoMask when the launch is a single wave of workgroups: C1 / C2;
+  // the batch configurations keep plain stores), 0 = plain, 1 = write-through wherever a variant exists,
+  // 0x100 | mask = write-through for the classes in mask (kStoreBit; per-class A/Bs). f5h_set_store_policy.
+  int store_policy = -1;
+  std::atomic<int64_t> n_store_wt{0}, n_store_plain{0};  // hot launches enqueued with write-through / plain stores
   // The chain's give-up word (chain.h): device memory of the engine, set by a chain wait that expired. The call's final
   // kernel then writes NaN results; a copy of it lands in a pinned host word (fault_host) at the end of every chained
   // call, and the engine's next call reads that word, fails with F5H_EHIP and switches the chain off.
@@ -592,6 +599,18 @@ static void layout(const f5h_engine* e, WS& ws, Bufs& b, int B, int N, int nfe, 
 
 // ---------------------------------------------------------------- probe
 enum { KC_FFN1 = 0, KC_ATTN = 1, KC_QKV = 2, KC_FFN2 = 3, KC_CONV = 4, KC_OUT = 5, KC_NORM = 6, KC_CHAIN = 7 };
+// Store policy: the class bits of f5h_set_store_policy's per-class form, and the classes the auto rule stores
+// write-through (what the per-class A/B at C2 kept, profiles/r07_ab_store_policy_c2.txt)
+static constexpr int kStoreBit(int kclass) {
+  return kclass == KC_QKV ? 1 : kclass == KC_ATTN ? 2 : kclass == KC_OUT ? 4 : kclass == KC_FFN1 ? 8 : kclass == KC_FFN2 ? 16 : 0;
+}
+static constexpr int kStoreAutoMask = 1 | 2 | 4 | 8 | 16;
+// what a class asks of gemm_store_wt / attention_store_wt under an engine policy
+static int store_want(int policy, int kclass) {
+  if (policy == 0 || policy == 1) return policy;
+  if (policy >= 0x100) return (policy & kStoreBit(kclass)) ? 1 : 0;
+  return (kStoreAutoMask & kStoreBit(kclass)) ? -1 : 0;
+}
 // Times one launch site when its kernel class is probed. With `kp` the kernel stamps itself
 // (GemmArgs/AttnArgs::probe); without, stamp kernels bracket the launch.
 struct ProbeScope {
@@ -631,6 +650,7 @@ struct Ctx {
   int site;  // probe launch-site counter, reset at the start of every step's enqueue
   int chain;  // this call may run the phase chain (engine switch, shape, and chain_admit's per-device check)
   int lnfold;  // this call runs the LayerNorm fold (engine switch, shape; never beside the chain)
+  int store;   // the engine's store policy at the start of the call
   double* hp;  // host milliseconds of the call by phase (kHostPhases, f5h_last_call_host_ms), or null
 };
 // Host time of an f5h_sample call by phase (f5h_last_call_host_ms): a call that blocks the host shows where.
@@ -909,6 +929,12 @@ static int backbone_part(Ctx& c, int s0, int ns, hipStream_t st) {
     g.ln_nparts = d / 64;
   };
   if (fold_on || rms_on) e->n_lnfold.fetch_add(1, std::memory_order_relaxed);
+  // store policy of a hot launch (its final arguments): write-through or plain stores
+  auto count_store = [&](int wt) { (wt ? e->n_store_wt : e->n_store_plain).fetch_add(1, std::memory_order_relaxed); };
+  auto gemm_policy = [&](GemmArgs& g, int epi, int kclass) {
+    g.store_wt = gemm_store_wt(bf, epi, g, store_want(c.store, kclass));
+    count_store(g.store_wt);
+  };
   for (int l = 0; l < a.depth; ++l) {
     Layer& Ly = e->layers[l];
     const float* ad = ada_k ? ada_k + (size_t)l * 6 * d : nullptr;
@@ -944,6 +970,7 @@ static int backbone_part(Ctx& c, int s0, int ns, hipStream_t st) {
         g.W = Ly.qkv_g.w;
         rms_consumer(g);
       }
+      gemm_policy(g, EPI_QKV, KC_QKV);
       ProbeScope ps(e, KC_QKV, st, &c.site, &g.probe);
       KCK(gemm(bf, EPI_QKV, g, st));
     }
@@ -962,6 +989,8 @@ static int backbone_part(Ctx& c, int s0, int ns, hipStream_t st) {
       at.q_len = (c.batch_mask && e->pad_skip) ? b.kvlen + s0 : nullptr;
       at.scale = 0.125f;
       at.prescaled = 1;
+      at.store_wt = attention_store_wt(bf, at, store_want(c.store, KC_ATTN));
+      count_store(at.store_wt);
       ProbeScope ps(e, KC_ATTN, st, &c.site, &at.probe);
       KCK(attention(bf, at, st));
     }
@@ -1007,6 +1036,7 @@ static int backbone_part(Ctx& c, int s0, int ns, hipStream_t st) {
       }
       if (fold_on) fold_producer(g, ad + 4 * d /*scale_mlp: hs = h (1 + scale_mlp) for FFN1*/);
       if (rms_on) rms_producer(g);  // the FFN-norm's statistics of h
+      gemm_policy(g, epi_resid, KC_OUT);
       ProbeScope ps(e, KC_OUT, st, &c.site, &g.probe);
       KCK(gemm(bf, epi_resid, g, st));
     }
@@ -1026,6 +1056,7 @@ static int backbone_part(Ctx& c, int s0, int ns, hipStream_t st) {
         g.W = Ly.ff1_g.w;
         rms_consumer(g);
       }
+      gemm_policy(g, EPI_GELU_TANH, KC_FFN1);
       ProbeScope ps(e, KC_FFN1, st, &c.site, &g.probe);
       KCK(gemm(bf, EPI_GELU_TANH, g, st));
     }
@@ -1035,6 +1066,7 @@ static int backbone_part(Ctx& c, int s0, int ns, hipStream_t st) {
       // the next layer's attention-norm: hs = h (1 + scale_msa of layer l + 1) for its QKV
       if (fold_on && l + 1 < a.depth) fold_producer(g, ada_k + (size_t)(l + 1) * 6 * d + d);
       if (rms_on && l + 1 < a.depth / 2) rms_producer(g);  // the next layer's attention-norm (its input is this h)
+      gemm_policy(g, epi_resid, KC_FFN2);
       ProbeScope ps(e, KC_FFN2, st, &c.site, &g.probe);
       KCK(gemm(bf, epi_resid, g, st));
     }
@@ -1450,6 +1482,7 @@ static GraphKey prologue_key(const Ctx& c, const void* ws) {
   key.use_cfg = c.use_cfg;
   key.batch_mask = c.batch_mask;
   key.lnfold = c.lnfold;
+  key.store = c.store;
   key.method = c.method;
   key.kernel_epoch = g_kernel_epoch.load();
   return key;
@@ -1563,6 +1596,7 @@ static int sample_impl(f5h_engine* e, void* stream, const f5h_sample_args* a, in
   ChainTicket ticket;  // (declared after `used`: its event is recorded first, both after every launch of the call)
   c.chain = chain_for_call(e, c, ticket);
   c.lnfold = e->lnfold && !c.chain && ((e->lnf_ok && !c.batch_mask) || e->rmsf_ok);
+  c.store = e->store_policy;
   double hp[kHostPhases] = {};
   c.hp = hp;
   const double h0 = host_ms();
@@ -1706,6 +1740,7 @@ static int run_steps(Ctx& c, const f5h_sample_args* a, const void* ws) {
   key.pad_skip = e->pad_skip;
   key.chain = c.chain;
   key.lnfold = c.lnfold;
+  key.store = c.store;
   key.method = c.method;
   key.kernel_epoch = g_kernel_epoch.load();
   std::memcpy(&key.cfg_bits, &a->cfg_strength, 4);
@@ -1897,6 +1932,7 @@ int f5h_forward(f5h_engine* e, void* stream, const f5h_forward_args* a, void* wo
   ChainTicket ticket;
   c.chain = chain_for_call(e, c, ticket);
   c.lnfold = e->lnfold && !c.chain && ((e->lnf_ok && !c.batch_mask) || e->rmsf_ok);
+  c.store = e->store_policy;
   const bool cached = a->text_cache == 2;
   if (a->t_dev) {  // time read on the stream: no host round trip (dit.py:332-333 takes a tensor)
     HIPCK(hipMemcpyAsync(c.b.tgrid, a->t_dev, sizeof(float), hipMemcpyDeviceToDevice, c.st));
@@ -1930,6 +1966,7 @@ int f5h_forward(f5h_engine* e, void* stream, const f5h_forward_args* a, void* wo
     key.pad_skip = e->pad_skip;
     key.chain = c.chain;
     key.lnfold = c.lnfold;
+    key.store = c.store;
     key.kernel_epoch = g_kernel_epoch.load();
     std::shared_ptr<GraphEntry> hold;
     RC(graph_get(c, key, false, body, hold, 1));
@@ -2064,6 +2101,29 @@ int f5h_ln_fold_stats(f5h_engine* e, int32_t* supported, int64_t* passes) {
   if (!e) return fail(F5H_EINVAL, "null engine");
   if (supported) *supported = (e->lnf_ok || e->rmsf_ok) ? 1 : 0;
   if (passes) *passes = e->n_lnfold.load(std::memory_order_relaxed);
+  return 0;
+}
+
+int f5h_set_store_policy(f5h_engine* e, int32_t mode) {
+  if (!e) return fail(F5H_EINVAL, "null engine");
+  if (mode != -1 && mode != 0 && mode != 1 && (mode < 0x100 || mode > 0x11F))
+    return fail(F5H_EINVAL, "store policy must be -1 (auto), 0 (plain), 1 (write-through) or 0x100 | class mask");
+  std::lock_guard<std::mutex> g(e->gm);
+  e->store_policy = mode;  // part of the step graph's key: a cached graph of another policy is not replayed
+  return 0;
+}
+
+int f5h_store_policy_stats(f5h_engine* e, int64_t* write_through, int64_t* plain) {
+  if (!e) return fail(F5H_EINVAL, "null engine");
+  if (write_through) *write_through = e->n_store_wt.load(std::memory_order_relaxed);
+  if (plain) *plain = e->n_store_plain.load(std::memory_order_relaxed);
+  return 0;
+}
+
+int f5h_store_policy_force(int32_t mode) {
+  if (mode < -1 || mode > 1) return fail(F5H_EINVAL, "forced store policy must be -1 (off), 0 (plain) or 1 (write-through)");
+  store_policy_force(mode);
+  g_kernel_epoch.fetch_add(1);  // captured graphs hold the old kernel choice
   return 0;
 }
 

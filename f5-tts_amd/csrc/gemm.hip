@@ -110,7 +110,34 @@ static bool hot_epi(int epi) {
 
 void gemm_force_config(int cfg) { g_force_cfg = cfg; }
 
-hipError_t gemm(int compute, int epi, const GemmArgs& a, hipStream_t st) {
+// ---- store policy (kernels.h): which launches store write-through
+static int g_store_force = -1;  // f5h_store_policy_force
+void store_policy_force(int mode) { g_store_force = mode; }
+int store_policy_forced() { return g_store_force; }
+
+// Does a write-through variant exist for this launch (launch_cfg), and how many tiles and resident block slots does
+// the chosen configuration have?
+static bool gemm_wt_variant(int compute, int epi, const GemmArgs& a, int64_t* tiles, int64_t* slots) {
+  if (compute == F5H_C_FP32 || (epi != EPI_QKV && epi != EPI_RESID16 && epi != EPI_GELU_TANH) || a.M <= 0) return false;
+  const int cfg = gemm_select_cfg(a);
+  if (cfg != 0 && cfg != 1 && cfg != 5) return false;
+  const int bm = cfg == 0 ? 64 : (cfg == 1 ? 128 : 192);
+  *tiles = (int64_t)((a.M + bm - 1) / bm) * ((a.N + 127) / 128);
+  *slots = 2 * (int64_t)gemm_num_cus();  // two 4-wave blocks per CU (gemm_kernel's launch bounds)
+  return epi == EPI_QKV ? fast_epi_ok<EPI_QKV>(a, 128)
+                        : (epi == EPI_RESID16 ? fast_epi_ok<EPI_RESID16>(a, 128) : fast_epi_ok<EPI_GELU_TANH>(a, 128));
+}
+
+int gemm_store_wt(int compute, int epi, const GemmArgs& a, int want) {
+  if (g_store_force >= 0) want = g_store_force;
+  int64_t tiles = 0, slots = 0;
+  if (want == 0 || !gemm_wt_variant(compute, epi, a, &tiles, &slots)) return 0;
+  return want > 0 || tiles <= slots;
+}
+
+hipError_t gemm(int compute, int epi, const GemmArgs& a0, hipStream_t st) {
+  GemmArgs a = a0;
+  if (g_store_force >= 0) a.store_wt = gemm_store_wt(compute, epi, a0, g_store_force);
   const int bke = compute ? 64 : 32;
   if (a.K % bke != 0 || a.M < 0 || a.N <= 0 || a.lda % 8 || a.ldw % 8) return hipErrorInvalidValue;
   // 8-column epilogue chunks: vector paths need 16 B alignment of every operand row

@@ -286,7 +286,8 @@ F5H_DEV void wait_stages(int n_stages) {
 
 // 16 bytes stored through a buffer descriptor: offsets past its extent are dropped by the hardware
 // range check, so out-of-range rows need no branch around the store
-// AUX: the cache-policy bits (kAuxWT: write-through, the in-launch hand-off's payload form)
+// AUX: the cache-policy bits (kAuxWT: write-through; the in-launch hand-off's payload form, and the store policy of
+// the single-wave launches, GemmArgs::store_wt)
 template <int AUX = 0>
 F5H_DEV void store16_rs(__amdgpu_buffer_rsrc_t r, uint32_t off, u32x4 v) {
   __builtin_amdgcn_raw_buffer_store_b128(v, r, off, 0, AUX);
@@ -638,9 +639,11 @@ F5H_DEV void epilogue_fast_t(const GemmArgs& g, const f32x4 (&acc)[MT][NT], floa
             q2 += dv * dv;
           }
           const float m2 = sum8(q2.x + q2.y);
-          // the row's 8 lanes store the same 8 bytes (no branch); rows >= M fall outside the descriptor
+          // the row's 8 lanes store the same 8 bytes (no branch); rows >= M fall outside the descriptor. A plain
+          // store under every policy: an 8-B write-through store is one fabric write each (2.7x a 16-B store's
+          // time per byte, MI355X_MICROARCH.md 'stores of each flavour'), and a launch issues one per row and strip
           __builtin_amdgcn_raw_buffer_store_b64(u32x2_t{__float_as_uint(mean), __float_as_uint(m2)}, ln_st,
-                                                (uint32_t)((row * ln_np + ln_p) * 8), 0, AUX);
+                                                (uint32_t)((row * ln_np + ln_p) * 8), 0, 0);
         }
       } else if constexpr (EPI == EPI_GELU_TANH || EPI == EPI_GELU_ERF_OP) {
         if constexpr (EPI == EPI_GELU_TANH && is16<TC>()) {
@@ -682,11 +685,13 @@ F5H_DEV void epilogue_fast_t(const GemmArgs& g, const f32x4 (&acc)[MT][NT], floa
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   });
 }
-template <typename TC, int EPI, int MT, int NT, int WN, int EPAD, bool PREF, int AUX = 0, int PD = 1, int PM, int PT>
+// FOLD: the fold forms are compiled in (not for the phase chain's kernels, which never run the fold)
+template <typename TC, int EPI, int MT, int NT, int WN, int EPAD, bool PREF, int AUX = 0, int PD = 1, bool FOLD = true,
+          int PM, int PT>
 F5H_DEV void epilogue_fast(const GemmArgs& g, const f32x4 (&acc)[MT][NT], float* Cs, int rbase, int cbase,
                            int lane, const V8 (&pre)[PM][PT], const float* ln_rows = nullptr) {
   // LayerNorm fold forms (GemmArgs hs / ln_part_in: 16-bit, 64-column wave strips; bias always present there)
-  if constexpr (WN == 64 && is16<TC>() && AUX == 0) {
+  if constexpr (WN == 64 && is16<TC>() && FOLD) {
     if constexpr (EPI == EPI_RESID16) {
       if (g.ln_part && g.ln_rms) {
         if (g.bias)
@@ -953,8 +958,9 @@ F5H_DEV void epilogue_direct(const GemmArgs& g, const f32x4 (&acc)[MT][NT], int 
 // image `lds`. PUB (the in-launch phase chain, chain.hip): stores are write-through and the tile's row groups are
 // published to dep.pub; a non-null dep.wait makes the block wait for its row groups' producers before its
 // first operand load; blocks past the last tile (the chain pads each phase to whole XCD rounds) do nothing.
+// AUX: the cache policy of the strip epilogue's stores (kAuxWT: the write-through store policy, launch_cfg).
 template <typename TC, int EPI, int BM, int BN, int WGM, int WGN, int NS, bool FAST, int KB, bool PUB = false,
-          bool CHAIN = false>
+          bool CHAIN = false, int AUX = 0>
 F5H_DEV void gemm_body(const GemmArgs& g, const int b, const int nwg, uint4* lds, const ChainDep& dep) {
   const ProbeT probe_t = probe_enter(g.probe);
   typedef GemmCfg<BM, BN, WGM, WGN, NS, KB> C;
@@ -1207,8 +1213,9 @@ F5H_DEV void gemm_body(const GemmArgs& g, const int b, const int nwg, uint4* lds
   constexpr bool FAST_EPI = FAST && NT % 2 == 0;
   static_assert(FAST_EPI || !PUB, "the chain publishes after the fast (LDS-strip) epilogue");
   if constexpr (FAST_EPI) {
-    epilogue_fast<TC, EPI, MT, NT, WN, C::EPAD, PREF, PUB ? kAuxWT : 0>(g, acc, Cs, m0 + wm * WM, n0 + wn * WN, lane,
-                                                                         pre, LNC ? ln_rows + 2 * wm * WM : nullptr);
+    static_assert(AUX == 0 || FAST_EPI, "the store policy exists for the strip epilogue only");
+    epilogue_fast<TC, EPI, MT, NT, WN, C::EPAD, PREF, PUB ? kAuxWT : AUX, 1, !PUB>(
+        g, acc, Cs, m0 + wm * WM, n0 + wn * WN, lane, pre, LNC ? ln_rows + 2 * wm * WM : nullptr);
     if constexpr (PUB) chain_publish(dep, g.M, m0, BM);
   }
   if constexpr (!FAST_EPI) {
@@ -1237,10 +1244,10 @@ F5H_DEV void gemm_body(const GemmArgs& g, const int b, const int nwg, uint4* lds
   probe_exit(g.probe, probe_t);
 }
 
-template <typename TC, int EPI, int BM, int BN, int WGM, int WGN, int NS, bool FAST = false, int KB = 128>
+template <typename TC, int EPI, int BM, int BN, int WGM, int WGN, int NS, bool FAST = false, int KB = 128, int AUX = 0>
 __global__ __launch_bounds__(64 * WGM * WGN, 2) void gemm_kernel(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) uint4 lds[GemmCfg<BM, BN, WGM, WGN, NS, KB>::bytes / 16];
-  gemm_body<TC, EPI, BM, BN, WGM, WGN, NS, FAST, KB>(g, blockIdx.x, gridDim.x, lds, ChainDep{});
+  gemm_body<TC, EPI, BM, BN, WGM, WGN, NS, FAST, KB, false, false, AUX>(g, blockIdx.x, gridDim.x, lds, ChainDep{});
 }
 
 // ======================================================================================
@@ -1926,6 +1933,13 @@ __global__ __launch_bounds__(512, 1) void gemm_8p_kernel(GemmArgs g) {
 template <typename TC, int EPI>
 static void launch_8p(const GemmArgs& a, hipStream_t st);
 
+// epilogues with a write-through variant of the 64x128 / 128x128 / 192x128 kernels (launch_cfg): what the 16-bit DiT
+// layer runs (QKV, the two residual GEMMs, FFN1), plain or with the LayerNorm fold
+template <typename TC, int EPI>
+constexpr bool store_wt_epi() {
+  return is16<TC>() && (EPI == EPI_QKV || EPI == EPI_RESID16 || EPI == EPI_GELU_TANH);
+}
+
 // the fast epilogue: whole-column tiles, 16-B aligned rows, destinations a buffer descriptor covers
 template <int EPI>
 static bool fast_epi_ok(const GemmArgs& a, int BN) {
@@ -1998,6 +2012,18 @@ static void launch_cfg(const GemmArgs& a, hipStream_t st) {
                        EPI == EPI_GELU_ERF_OP || EPI == EPI_STORE || EPI == EPI_STORE16 || EPI == EPI_INPROJ;
   if constexpr (HOT) {
     if (fast_epi_ok<EPI>(a, BN)) {
+      // Store policy (GemmArgs::store_wt): a second, separately compiled kernel whose strip-epilogue stores are
+      // write-through, for the epilogues of the 16-bit DiT layer. Only these 2-blocks-per-CU configurations have
+      // it: the 256x256 kernels of the large batches (cfg 11 / 12 / 13) run many waves of tiles per CU, so the
+      // write-back of one tile already overlaps the next tile's main loop, and write-through stores would only
+      // cost their consumers the lines the plain stores leave in the XCD's L2.
+      if constexpr (store_wt_epi<TC, EPI>()) {
+        if (a.store_wt) {
+          hipLaunchKernelGGL((gemm_kernel<TC, EPI, BM, BN, WGM, WGN, NS, true, KB, kAuxWT>), dim3(tiles),
+                             dim3(64 * WGM * WGN), 0, st, a);
+          return;
+        }
+      }
       hipLaunchKernelGGL((gemm_kernel<TC, EPI, BM, BN, WGM, WGN, NS, true, KB>), dim3(tiles), dim3(64 * WGM * WGN), 0,
                          st, a);
       return;

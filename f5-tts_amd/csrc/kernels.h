@@ -81,6 +81,10 @@ struct GemmArgs {
   // its W already carries the gain (W' = W diag(g), built once), ln_u / ln_v are null (0) and rstd = 1 / sqrt(ss / d +
   // ln_eps). ln_eps: the consumer's variance epsilon (LayerNorm: 1e-6, modules.py:316,336).
   int ln_rms; float ln_eps;
+  // Store policy: 1 = the epilogue's stores are write-through (sc1) where the launch has such a variant
+  // (EPI_QKV / EPI_RESID16 / EPI_GELU_TANH in the 16-bit 64x128, 128x128 and 192x128 kernels), 0 = plain stores.
+  // Same values either way. Set from gemm_store_wt (DESIGN.md §3 'Launch boundaries').
+  int store_wt;
 };
 
 // Does the row tile [m0, m0 + BM) of an M-row GEMM hold a live row? Sequence s (rows [s*live_seq, (s+1)*live_seq))
@@ -104,6 +108,19 @@ hipError_t gemm(int compute, int epi, const GemmArgs& a, hipStream_t st);
 // pin the 16-bit GEMM tile configuration (0, 1, 5, 11, 12, 13; -1 = automatic choice); tuning and test hook
 void gemm_force_config(int cfg);
 
+
+// Store policy of the hot-path producers (DESIGN.md §3 'Launch boundaries'). A launch that is a single wave of
+// workgroups (grid <= the resident block slots of its configuration) writes nothing back until its end-of-kernel
+// release, which then flushes every dirty byte of the XCD L2s in one burst with all CUs idle; with write-through
+// stores the write-back runs under the epilogue and the kernel boundary stays the only synchronisation.
+// want: 0 = plain, 1 = write-through wherever a variant exists, -1 = write-through when a variant exists and the
+// launch is a single wave. Returns the store_wt to put into the launch's arguments. store_policy_force (test / A/B
+// hook, f5h_store_policy_force): mode >= 0 replaces every `want`, also for launches whose arguments were built
+// without asking (the op entry points); -1 = as asked.
+int gemm_store_wt(int compute, int epi, const GemmArgs& a, int want);
+void store_policy_force(int mode);
+int store_policy_forced();
+
 // attention: Q,K,V [S,H,L,64] operand dtype; O [S,L,H*64] operand dtype.
 struct AttnArgs {
   const void* q; const void* k; const void* v; void* o;
@@ -116,8 +133,10 @@ struct AttnArgs {
   int prescaled;          // q already carries scale*log2(e): scores are in log2 units
   DevProbe probe;         // in-kernel launch timing (null slots: off)
   int force_safe;         // test hook: every workgroup reruns its key loop in the lazy-max form (attention.hip)
+  int store_wt;           // store policy: 1 = O is stored write-through (16-bit kernel), 0 = plain; attention_store_wt
 };
 hipError_t attention(int compute, const AttnArgs& a, hipStream_t st);
+int attention_store_wt(int compute, const AttnArgs& a, int want);  // as gemm_store_wt
 // test hook (f5h_attn_force_safe): 1 = every later 16-bit attention launch takes the SAFE rerun
 void attention_force_safe(int on);
 

@@ -51,6 +51,9 @@ EXPORTS = (
     "f5h_chain_debug_spin_limit",
     "f5h_set_ln_fold",
     "f5h_ln_fold_stats",
+    "f5h_set_store_policy",
+    "f5h_store_policy_stats",
+    "f5h_store_policy_force",
     "f5h_op_linear",
     "f5h_op_attention",
     "f5h_op_attention_qlen",
@@ -244,6 +247,13 @@ def lib():
         L.f5h_set_ln_fold.restype = ctypes.c_int
         L.f5h_ln_fold_stats.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i64)]
         L.f5h_ln_fold_stats.restype = ctypes.c_int
+    if hasattr(L, "f5h_set_store_policy"):
+        L.f5h_set_store_policy.argtypes = [vp, i32]
+        L.f5h_set_store_policy.restype = ctypes.c_int
+        L.f5h_store_policy_stats.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64)]
+        L.f5h_store_policy_stats.restype = ctypes.c_int
+        L.f5h_store_policy_force.argtypes = [i32]
+        L.f5h_store_policy_force.restype = ctypes.c_int
     if hasattr(L, "f5h_chain_debug_spin_limit"):
         L.f5h_chain_debug_spin_limit.argtypes = [i64]
         L.f5h_chain_debug_spin_limit.restype = ctypes.c_int

@@ -154,6 +154,23 @@ class Engine:
         _lib.check(_lib.lib().f5h_ln_fold_stats(self._h, ctypes.byref(sup), ctypes.byref(n)), "ln_fold_stats")
         return bool(sup.value), int(n.value)
 
+    # class bits of set_store_policy's per-class form (0x100 | mask)
+    STORE_CLASS_BITS = {"qkv": 1, "attn": 2, "out": 4, "ffn1": 8, "ffn2": 16}
+
+    def set_store_policy(self, mode: int):
+        """Store policy of the layer's hot launches (f5h_set_store_policy; DESIGN.md §3 'Launch boundaries'): -1 = auto
+        (write-through stores when the launch is a single wave of workgroups, i.e. single-utterance calls), 0 = plain
+        stores, 1 = write-through wherever a kernel variant exists, 0x100 | mask = write-through for the classes in
+        mask (STORE_CLASS_BITS; A/B runs). Results are bitwise identical under every policy."""
+        _lib.check(_lib.lib().f5h_set_store_policy(self._h, int(mode)), "set_store_policy")
+
+    def store_policy_stats(self):
+        """(hot launches this engine enqueued with write-through stores, with plain stores); eager launches and
+        graph captures count, replays do not."""
+        wt, plain = ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(_lib.lib().f5h_store_policy_stats(self._h, ctypes.byref(wt), ctypes.byref(plain)), "store_policy_stats")
+        return int(wt.value), int(plain.value)
+
     def chain_stats(self):
         """(phase-chain launches this engine enqueued, 1 if one of its chain waits gave up and the engine has not
         reported it yet, chained calls of this process that the per-device concurrency rule sent to the separate
@@ -308,12 +325,13 @@ def op_linear(A, W, bias=None, compute="bf16"):
     return C
 
 
-def op_attention(Q, K, V, kv_len=None, compute="bf16", q_prescaled=False, poison=False, q_len=None):
+def op_attention(Q, K, V, kv_len=None, compute="bf16", q_prescaled=False, poison=False, q_len=None, return_ws=False):
     """O[S,N,H*64] = softmax(Q K^T/8) V; q_prescaled: Q already carries (1/8)*log2(e). poison: fill the
     workspace (16-bit q | k | v | o, back to back) with NaN bits first, so a kernel that reads key rows past N
     (the next (sequence, head)'s rows, or past V into O) turns its output NaN. q_len [S]: live query rows per
     sequence (the batch path's pad skip); with poison, O is NaN as well before the call, so rows the kernel
-    leaves unwritten come back NaN in every compute mode."""
+    leaves unwritten come back NaN in every compute mode. return_ws: (O, the workspace bytes) — past the 16-bit o
+    (8 bytes per element of Q in all) nothing is ever written, so a poisoned workspace keeps its 0xFF there."""
     S, H, N, D = Q.shape
     assert D == 64
     O = torch.empty(S, N, H * 64, dtype=torch.float32, device=Q.device)
@@ -326,7 +344,7 @@ def op_attention(Q, K, V, kv_len=None, compute="bf16", q_prescaled=False, poison
                                                Q.contiguous().data_ptr(), K.contiguous().data_ptr(),
                                                V.contiguous().data_ptr(), _lib.ptr(kv), int(bool(q_prescaled)),
                                                O.data_ptr(), ws.data_ptr(), ws.numel()), "f5h_op_attention")
-        return O
+        return (O, ws) if return_ws else O
     if poison:
         O.fill_(float("nan"))
     ql = q_len.to(Q.device, torch.int32).contiguous()
@@ -335,7 +353,7 @@ def op_attention(Q, K, V, kv_len=None, compute="bf16", q_prescaled=False, poison
                                                 V.contiguous().data_ptr(), _lib.ptr(kv), ql.data_ptr(),
                                                 int(bool(q_prescaled)), O.data_ptr(), ws.data_ptr(), ws.numel()),
                "f5h_op_attention_qlen")
-    return O
+    return (O, ws) if return_ws else O
 
 
 def _f32(t, dev=None):
@@ -411,7 +429,7 @@ EPI = {"store": 0, "silu": 1, "gelu_tanh": 2, "gelu_erf": 3, "resid": 4, "resid_
 def op_gemm_epi(epi, A, W, bias=None, C=None, compute="bf16", A2=None, k_split=0, resid=None, gate=None, rowkeep=None,
                 live_len=None, live_seq=0, add=None, dual_rows=0, seq_len=0, heads=0, rope_heads=0, q_scale=0.0,
                 hs_scale=None, ln_producer=False, ln_part_in=None, ln_u=None, ln_v=None, ln_rms=False, ln_eps=0.0,
-                ln_nparts=None, poison=False):
+                ln_nparts=None, poison=False, ws_fill=None, return_ws=False):
     """A GEMM with epilogue `epi` (a key of EPI; f5h_op_gemm_epi). The in/out epilogues update a copy of C and
     return it; "inproj" returns C [M + dual_rows, N]; "qkv" returns (q, k, v [S,H,L,64], rope [L,32,2]).
 
@@ -419,7 +437,10 @@ def op_gemm_epi(epi, A, W, bias=None, C=None, compute="bf16", A2=None, k_split=0
     parts) with parts [M + OP_GUARD_ROWS, N / 64, 2] the strips' (mean, M2) and hs [M + OP_GUARD_ROWS, N] =
     round(C (1 + hs_scale)) (None with ln_rms, which writes none); the guard rows past M start as NaN, the live rows
     too with poison. ln_part_in [M, K / 64, 2] ("gelu_tanh" / "qkv"): the consumer, with ln_u, ln_v [N] (LayerNorm
-    form) or ln_rms, and the variance epsilon ln_eps. ln_nparts overrides the strip count (validation tests)."""
+    form) or ln_rms, and the variance epsilon ln_eps. ln_nparts overrides the strip count (validation tests).
+    ws_fill: byte the workspace is filled with before the call; return_ws: the workspace is appended to the result
+    (its buffers are taken in f5h_op_gemm_epi's order, each from a multiple of 256 bytes; the bytes past the last one
+    are never written)."""
     M, K = A.shape
     N = W.shape[0]
     dev = A.device
@@ -466,9 +487,12 @@ def op_gemm_epi(epi, A, W, bias=None, C=None, compute="bf16", A2=None, k_split=0
         a.C = C.data_ptr()
         out = C
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    if ws_fill is not None:
+        ws.fill_(int(ws_fill))
     _lib.check(_lib.lib().f5h_op_gemm_epi(_lib.stream_handle(dev), ctypes.byref(a), ws.data_ptr(), ws.numel()),
                "f5h_op_gemm_epi")
-    return (out, hs, parts) if ln_producer else out
+    res = (out, hs, parts) if ln_producer else out
+    return (res, ws) if return_ws else res
 
 
 def op_lnfold_uv(table, W1, Wqkv, nfe, out_off, compute="bf16"):
@@ -507,6 +531,12 @@ def attn_force_safe(on: bool):
 def gemm_force_config(cfg: int = -1):
     """Pin the 16-bit GEMM tile configuration (0, 1, 5, 11, 12, 13) for this process; -1 = automatic."""
     _lib.check(_lib.lib().f5h_gemm_force_config(int(cfg)), "gemm_force_config")
+
+
+def store_policy_force(mode: int = -1):
+    """Test / A/B hook: every later GEMM and attention launch of this process (the op entry points included) stores
+    plain (0) or write-through wherever a variant exists (1); -1 = as the caller (the engine's policy) chose."""
+    _lib.check(_lib.lib().f5h_store_policy_force(int(mode)), "store_policy_force")
 
 
 def chain_debug_spin_limit(limit: int = -1):

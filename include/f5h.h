@@ -268,6 +268,20 @@ int f5h_set_chain(f5h_engine* eng, int32_t enable);
  * 64, or 16-bit UNetT with dim a multiple of 64; dim <= 1024), *passes = backbone passes enqueued with a fold. */
 int f5h_set_ln_fold(f5h_engine* eng, int32_t enable);
 int f5h_ln_fold_stats(f5h_engine* eng, int32_t* supported, int64_t* passes);
+/* Store policy of a layer's five hot launches (QKV, attention, out-proj, FFN1, FFN2; 16-bit modes). A launch that is
+ * a single wave of workgroups writes nothing back until its end-of-kernel release flushes every dirty byte at once,
+ * with all compute units idle; the write-through variants of those kernels store with the sc1 cache policy, so the
+ * write-back runs under the epilogue. Values are bitwise identical under every policy.
+ * mode: -1 = auto (default): write-through when the launch is a single wave (grid <= resident workgroup slots of
+ * its configuration: single-utterance calls; batches keep plain stores), 0 = plain stores, 1 = write-through wherever
+ * a variant exists, 0x100 | mask = write-through for the classes in mask (1 QKV, 2 attention, 4 out-proj, 8 FFN1,
+ * 16 FFN2; for A/B runs). The policy is part of the step graph's key. f5h_store_policy_stats: hot launches enqueued
+ * (eager launches and graph captures, not replays) with write-through and with plain stores.
+ * f5h_store_policy_force: process-wide test hook beside f5h_gemm_force_config; mode 0 / 1 overrides every engine's
+ * policy and also applies to the op entry points (f5h_op_gemm_epi, f5h_op_attention*), -1 = off. */
+int f5h_set_store_policy(f5h_engine* eng, int32_t mode);
+int f5h_store_policy_stats(f5h_engine* eng, int64_t* write_through, int64_t* plain);
+int f5h_store_policy_force(int32_t mode);
 /* Failure of the chain (never expected): a chain wait that gives up (a bounded spin of ~0.3 s) sets the
  * ENGINE's fault word; that call's `out` (f5h_sample) / `pred` (f5h_forward) is then all NaN, and the engine's
  * next f5h_sample / f5h_forward fails with F5H_EHIP (message in f5h_last_error), clears the word and turns the

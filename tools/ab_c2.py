@@ -4,8 +4,14 @@ arm's output is bitwise identical to the first arm's.
 
     python tools/ab_c2.py [--config c2] [--rounds 5] [--calls 5] [--arms streams1,streams2]
 Arms: streams1 / streams2 (f5h_set_cfg_streams), gemmN (f5h_gemm_force_config N, -1 = auto),
-eager (step graph off), chain0 / chain1 (f5h_set_chain), fold0 / fold1 (f5h_set_ln_fold). Outputs are compared for the warm call (a graph capture)
+eager (step graph off), chain0 / chain1 (f5h_set_chain), fold0 / fold1 (f5h_set_ln_fold), wt0 / wt1 / wtauto
+(f5h_set_store_policy: plain stores, write-through wherever a variant exists, the shipped rule) and wt:<classes>
+(write-through for the named classes only, e.g. wt:qkv or wt:qkv+ffn1; classes qkv, attn, out, ffn1, ffn2). The two
+store policies are separately compiled kernels chosen on the host, so neither arm carries a switch. Every other arm
+runs the shipped (auto) store policy. Outputs are compared for the warm call (a graph capture)
 AND the last timed call of every arm (graph replays only: round 6 found a bug that only replays showed).
+Besides the median and minimum, the spread (max - min of the per-round means) of every arm is printed: a difference
+between two arms counts only beyond twice the spread of the baseline arm.
 """
 import argparse
 import os
@@ -31,7 +37,7 @@ def main():
     ap.add_argument("--arms", default="streams1,streams2")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
-    case = {"c2": synthetic.c2_case, "c3": synthetic.c3_case, "c4": synthetic.c4_case, "c5": synthetic.c5_case}[a.config]()
+    case = {"c1": synthetic.c1_case, "c2": synthetic.c2_case, "c3": synthetic.c3_case, "c4": synthetic.c4_case, "c5": synthetic.c5_case}[a.config]()
     model, arch = bench.build_model(case["preset"], a.compute, dev)
     B = case["B"]
     refs = case["ref"] if isinstance(case["ref"], list) else [case["ref"]] * B
@@ -51,6 +57,12 @@ def main():
             eng.set_chain(arm == "chain1")
         if arm.startswith("fold"):
             eng.set_ln_fold(arm == "fold1")
+        policy = -1
+        if arm in ("wt0", "wt1"):
+            policy = int(arm[2:])
+        elif arm.startswith("wt:"):
+            policy = 0x100 | sum(eng.STORE_CLASS_BITS[c] for c in arm[3:].split("+"))
+        eng.set_store_policy(policy)
 
     outs, lasts, times = {}, {}, {arm: [] for arm in arms}
     for arm in arms:  # warm every arm (graph capture) before timing
@@ -74,7 +86,8 @@ def main():
         same = torch.equal(outs[arm], outs[arms[0]]) and torch.equal(lasts[arm], outs[arms[0]])
         ref = outs[arms[0]].float()
         rel = float((lasts[arm].float() - ref).norm() / ref.norm())
-        print(f"{arm:10s} median {t[len(t) // 2]:8.3f} ms  min {t[0]:8.3f} ms  bitwise-equal-to-{arms[0]} {same} "
+        print(f"{arm:10s} median {t[len(t) // 2]:8.3f} ms  min {t[0]:8.3f} ms  spread {t[-1] - t[0]:6.3f} ms  "
+              f"bitwise-equal-to-{arms[0]} {same} "
               f"(warm and last timed call; rel-L2 of the last {rel:.3e})", flush=True)
 
 
