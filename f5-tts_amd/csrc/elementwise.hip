@@ -495,6 +495,69 @@ hipError_t text_embed(const TextEmbArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------- text average upsampling
+// One block per sequence. Pass 1: thread t counts the valid tokens of its contiguous run of positions; an exclusive
+// scan of the 256 counts gives every run its first slot in the compacted position list (LDS, N <= 8192 entries).
+// Pass 2: one wave per frame n computes its token by the closed form of the reference's repeat loop,
+//   first = (T - rem) base frames of the base-times tokens: j = n / base there (never reached when base == 0),
+//   j = (T - rem) + (n - first) / (base + 1) after them,
+// and copies row pos[j] of both branches (or zeros past audio_len / with no valid token).
+constexpr int kTextUpMaxN = 8192;
+__global__ __launch_bounds__(256) void text_upsample_kernel(TextUpArgs a) {
+  __shared__ unsigned short pos[kTextUpMaxN];
+  __shared__ int cnt[256];
+  __shared__ int total;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int audio_len = a.seq_len ? min(max(a.seq_len[b], 0), a.N) : a.N;
+  auto valid_tok = [&](int n) {  // as text_embed_kernel: filler 0 after the +1 shift, positions past seq_len are filler
+    return n < a.nt && n < audio_len && a.text[(int64_t)b * a.nt + n] + 1 != 0;
+  };
+  const int per = (a.N + 255) / 256, n0 = tid * per, n1 = min(n0 + per, a.N);
+  int c = 0;
+  for (int n = n0; n < n1; ++n) c += valid_tok(n) ? 1 : 0;
+  cnt[tid] = c;
+  __syncthreads();
+  if (tid == 0) {
+    int run = 0;
+    for (int t = 0; t < 256; ++t) {
+      const int v = cnt[t];
+      cnt[t] = run;
+      run += v;
+    }
+  }
+  __syncthreads();
+  int slot = cnt[tid];
+  for (int n = n0; n < n1; ++n)
+    if (valid_tok(n)) pos[slot++] = (unsigned short)n;
+  if (tid == 255) total = slot;  // the last run's end: the number of valid tokens
+  __syncthreads();
+  const int Tn = total;
+  const int base = Tn > 0 ? audio_len / Tn : 0, rem = Tn > 0 ? audio_len % Tn : 0;
+  const int first = (Tn - rem) * base;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int64_t seq = (int64_t)b * a.N;
+  for (int n = wave; n < a.N; n += 4) {
+    int src = -1;
+    if (Tn > 0 && n < audio_len) {
+      const int j = n < first ? n / max(base, 1) : (Tn - rem) + (n - first) / (base + 1);
+      src = pos[min(j, Tn - 1)];
+    }
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int q = lane; q < a.td / 4; q += 64) {
+      const int64_t o = (seq + n) * a.td + 4 * q, i = (seq + max(src, 0)) * a.td + 4 * q;
+      *reinterpret_cast<float4*>(a.out_c + o) = src >= 0 ? *reinterpret_cast<const float4*>(a.in_c + i) : z;
+      if (a.out_u) *reinterpret_cast<float4*>(a.out_u + o) = src >= 0 ? *reinterpret_cast<const float4*>(a.in_u + i) : z;
+    }
+  }
+}
+hipError_t text_upsample(const TextUpArgs& a, hipStream_t st) {
+  if (a.B <= 0 || a.N <= 0 || a.N > kTextUpMaxN || a.td <= 0 || a.td % 4 || a.nt < 0 || !a.in_c || !a.out_c ||
+      (a.out_u && !a.in_u))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(text_upsample_kernel, dim3(a.B), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
 // ConvNeXtV2Block front half (modules.py:260-264): depthwise Conv1d(k7, pad3) + bias -> LayerNorm(affine)
 template <typename TO>
 __global__ void dwconv_ln_kernel(const float* x, int S, int L, int C, const float* w, const float* bias,

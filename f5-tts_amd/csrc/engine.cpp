@@ -66,6 +66,7 @@ struct Layer {
   Lin qkv, out, ff1, ff2, skip;  // skip: UNetT skip_proj [d][2d] over cat(x, skip) (later half)
   float *g_attn = nullptr, *g_ff = nullptr;  // UNetT RMSNorm gains
   Lin qkv_g, ff1_g;  // UNetT RMSNorm fold: qkv / ff1 with the norm's gain folded in, W diag(g) (same bias)
+  float *q_norm_w = nullptr, *k_norm_w = nullptr;  // qk_norm = "rms_norm": the [64] gains of q_norm / k_norm (fp32)
 };
 
 struct GraphKey {
@@ -92,6 +93,7 @@ struct f5h_engine {
   std::vector<void*> allocs;  // device memory from the stream-ordered pool (dev_alloc), freed by the reaper
   hipStream_t mstream = nullptr;  // the engine's own stream: creation-time uploads/packing, frees at release
   Lin t1, t2, ada, in_x, in_ct, proj_out;
+  Lin long_skip;  // DiT long_skip_connection [d][2d] over cat(x, kept input embedding) (dit.py:228, 364-365)
   float* text_table = nullptr;
   float* freqs = nullptr;
   std::vector<CNX> cnx;
@@ -451,6 +453,13 @@ static int pack_all(f5h_engine* e, const WMap& W) {
     if (!wq || !wk || !wv || !bq || !bk || !bv) return fail(F5H_ENOWEIGHT, err);
     RC(make_lin(e, {Block{wq, inner, d, 0, d, 0}, Block{wk, inner, d, 0, d, 0}, Block{wv, inner, d, 0, d, 0}}, d,
                 {bq, bk, bv}, &L.qkv));
+    if (a.qk_norm) {  // RMSNorm(dim_head) gains, shared by the layer's heads (modules.py:402-407)
+      for (int j = 0; j < 2; ++j) {
+        const std::string n = pa + (j ? "k_norm.weight" : "q_norm.weight");
+        if (!W.get(n, a.dim_head, &err)) return fail(F5H_EINVAL, "qk_norm: " + err);
+        RC(vec_upload(e, W, n, a.dim_head, j ? &L.k_norm_w : &L.q_norm_w, &err));
+      }
+    }
     RC(lin_simple(e, W, pa + "to_out.0.weight", pa + "to_out.0.bias", d, inner, &L.out, &err));
     RC(lin_simple(e, W, pf + "0.0.weight", pf + "0.0.bias", F, d, &L.ff1, &err));
     RC(lin_simple(e, W, pf + "2.weight", pf + "2.bias", d, F, &L.ff2, &err));
@@ -477,6 +486,11 @@ static int pack_all(f5h_engine* e, const WMap& W) {
     ada_blocks.push_back(Block{nw, 2 * d, d, 0, d, 0});
     ada_bias.push_back(nb);
     RC(make_lin(e, ada_blocks, d, ada_bias, &e->ada));
+    if (a.long_skip_connection) {
+      const WView* sw = W.get("long_skip_connection.weight", (int64_t)d * 2 * d, &err);
+      if (!sw) return fail(F5H_EINVAL, "long_skip_connection: " + err);
+      RC(make_lin(e, {Block{sw, d, 2 * d, 0, 2 * d, 0}}, 2 * d, {}, &e->long_skip));
+    }
   } else {
     RC(vec_upload(e, W, "norm_out.g", d, &e->norm_out_g, &err));
   }
@@ -519,6 +533,10 @@ struct Bufs {
   float** trajp;                      // device slot: trajectory base pointer (or null)
   // midpoint / rk4 only: the step grid [steps + 1] (tgrid then holds the evaluation times) and the kept slopes
   float *sgrid, *kbuf;
+  // DiT options (null without them): the residual stream as it stood after the input embedding, kept for the
+  // long skip connection (residual dtype); the text embedding after average upsampling [2][B][N][td]
+  void* hkeep;
+  float* te_up;
   // UNetT residual stream (operand dtype): xs[0..depth/2] -- layer l < depth/2 reads xs[l] (its
   // skip connection, kept) and writes xs[l+1]; later layers ping-pong between pp[0] and pp[1]
   std::vector<void*> xs;
@@ -595,6 +613,9 @@ static void layout(const f5h_engine* e, WS& ws, Bufs& b, int B, int N, int nfe, 
   b.sgrid = method ? ws.take<float>((size_t)steps + 1) : nullptr;
   const int kept = ode_kept_slopes(method);
   b.kbuf = kept ? ws.take<float>((size_t)kept * B * N * a.mel_dim) : nullptr;
+  // the options' buffers come last, so every other buffer sits where it does without them
+  b.hkeep = a.long_skip_connection ? ws.take<char>(rows * d * es) : nullptr;
+  b.te_up = a.text_average_upsampling ? ws.take<float>((size_t)2 * B * N * td) : nullptr;
 }
 
 // ---------------------------------------------------------------- probe
@@ -754,9 +775,25 @@ static int prologue(Ctx& c, const float* t_host, int nt_vals, const float* cond,
       g.rowkeep = a.text_mask_padding ? b.keepfill : nullptr;
       KCK(gemm(bf, EPI_RESID_FILL, g, st));
     }
+    // text_embedding_average_upsampling (dit.py:55-84, 131-137): both branches, by the mask taken before drop_text
+    if (a.text_average_upsampling) {
+      TextUpArgs u{};
+      u.text = text;
+      u.B = c.B;
+      u.nt = c.nt;
+      u.N = c.N;
+      u.td = td;
+      u.seq_len = t.seq_len;
+      u.in_c = t.out_c;
+      u.in_u = t.out_u;
+      u.out_c = b.te_up;
+      u.out_u = b.te_up + (size_t)c.B * c.N * td;
+      KCK(text_upsample(u, st));
+    }
   }
   // ---- hoisted input projection: P = [step_cond | text] . W_ct^T + b
-  KCK(build_ct(bf, cond, cond_mask, b.te, b.te + (size_t)c.B * c.N * td, c.B, c.N, td, c.S, c.drop_audio,
+  const float* te = a.text_average_upsampling ? b.te_up : b.te;
+  KCK(build_ct(bf, cond, cond_mask, te, te + (size_t)c.B * c.N * td, c.B, c.N, td, c.S, c.drop_audio,
                c.drop_text, b.act, st));
   GemmArgs g = gargs(b.act, 128 + e->tdp, e->in_ct, c.S * c.N, b.P, d);
   KCK(gemm(bf, EPI_STORE, g, st));
@@ -854,6 +891,14 @@ static int backbone_part(Ctx& c, int s0, int ns, hipStream_t st) {
     KCK(conv_pos(bf, cv, st));
   }
   if (!dit) KCK(write_time_token(bf, r16, b.temb_cur, ns, c.L, d, bh, st));
+  // long_skip_connection (dit.py:354-355): the stream as it stands after the input embedding, kept for the whole
+  // evaluation (a copy: the layers update the stream in place)
+  void* hkeep = a.long_skip_connection ? (char*)b.hkeep + ro * d * hsz : nullptr;
+  if (hkeep) {
+    if (bf != 0 && !r16)
+      return fail(F5H_EINVAL, "long_skip_connection: F5H_RES32 (fp32 residual under 16-bit operands) is not supported");
+    KCK(hipMemcpyAsync(hkeep, bh, (size_t)rows * d * hsz, hipMemcpyDeviceToDevice, st));
+  }
 
   const float* ada_k = dit ? b.ada_cur : nullptr;
   const int epi_resid = r16 ? EPI_RESID16 : EPI_RESID;
@@ -869,6 +914,9 @@ static int backbone_part(Ctx& c, int s0, int ns, hipStream_t st) {
     g.k = k;
     g.v = v;
     g.q_scale = 0.125f * 1.4426950408889634f;  // softmax scale 1/sqrt(64) in log2 units, folded into q
+    g.q_norm_w = Lq.q_norm_w;  // qk_norm (null without it): RMSNorm of every q / k head ahead of RoPE
+    g.k_norm_w = Lq.k_norm_w;
+    g.qk_norm_eps = 1e-6f;     // modules.py:406-407
     return g;
   };
   // In-launch phase chain (chain.hip): a layer's out-proj .. FFN2 plus the next layer's LayerNorm + QKV (or
@@ -1073,6 +1121,16 @@ static int backbone_part(Ctx& c, int s0, int ns, hipStream_t st) {
   }
   if (dit) {
     const float* fin = ada_k + (size_t)a.depth * 6 * d;  // AdaLayerNorm_Final: (scale, shift)
+    if (hkeep) {
+      // x = long_skip_connection(cat(x, kept)) (dit.py:364-365): ONE GEMM over K = 2d whose A columns [d, 2d) come
+      // from the kept buffer (as the UNetT skip projection above), into the free first conv buffer
+      void* hl = (char*)b.c1 + no * d * hsz;
+      GemmArgs g = gargs(h, d, e->long_skip, rows, hl, d);
+      g.A2 = hkeep;
+      g.k_split = d;
+      KCK(gemm(bf, r16 ? EPI_STORE16 : EPI_STORE, g, st));
+      h = hl;
+    }
     if (!final_done) KCK(ln_modulate(bf, h, r16, rows, d, fin + d, fin, aop, st));
   } else {
     KCK(rms_norm_g(bf, h, r16, rows, d, e->norm_out_g, aop, st));
@@ -1199,8 +1257,10 @@ static int chain_for_call(f5h_engine* e, const Ctx& c, ChainTicket& t) {
     return v && *v == '1';
   }();
   const bool split = e->graph_mode && e->split_cfg == 1 && c.use_cfg;  // the two CFG parts: no chain
+  // qk_norm / long_skip_connection: the chain's own QKV phase has no norm and its last launch carries the final
+  // LayerNorm, which the long skip projection must precede: such engines always take the separate launches
   if (!e->chain || e->a.backbone != F5H_DIT || e->bf == 0 || res32 || e->a.dim != 1024 || c.batch_mask || split ||
-      !e->chain_fault)
+      !e->chain_fault || e->a.qk_norm || e->a.long_skip_connection)
     return 0;
   if (!chain_admit(e->dev, c.st)) return 0;
   t.dev = e->dev;
@@ -1243,6 +1303,14 @@ static int check_arch(const f5h_arch* a) {
   if (a->backbone == F5H_UNETT && a->conv_layers != 0) return fail(F5H_EINVAL, "UNetT with conv_layers unsupported");
   if (a->compute != F5H_FP32 && a->compute != F5H_BF16 && a->compute != F5H_FP16)
     return fail(F5H_EINVAL, "compute must be FP32, BF16 or FP16");
+  if (a->qk_norm != 0 && a->qk_norm != 1) return fail(F5H_EINVAL, "qk_norm must be 0 (none) or 1 (rms_norm)");
+  if ((a->long_skip_connection != 0 && a->long_skip_connection != 1) ||
+      (a->text_average_upsampling != 0 && a->text_average_upsampling != 1))
+    return fail(F5H_EINVAL, "long_skip_connection and text_average_upsampling must be 0 or 1");
+  if (a->backbone != F5H_DIT && (a->long_skip_connection || a->text_average_upsampling))
+    return fail(F5H_EINVAL, "long_skip_connection and text_average_upsampling are DiT options");
+  if (a->text_average_upsampling && !a->text_mask_padding)
+    return fail(F5H_EINVAL, "text_embedding_average_upsampling requires text_mask_padding to be True");
   return 0;
 }
 
@@ -2429,6 +2497,11 @@ int f5h_op_gemm_epi(void* stream, const f5h_op_gemm_args* a, void* workspace, si
   } else if (!a->C) {
     return fail(F5H_EINVAL, "op_gemm_epi: null C");
   }
+  if (a->q_norm_w || a->k_norm_w) {
+    if (epi != EPI_QKV) return fail(F5H_EINVAL, "op_gemm_epi: q_norm_w / k_norm_w go with EPI_QKV");
+    if (!a->q_norm_w || !a->k_norm_w) return fail(F5H_EINVAL, "op_gemm_epi: qk_norm needs q_norm_w and k_norm_w");
+    if (!(a->qk_norm_eps >= 0.f)) return fail(F5H_EINVAL, "op_gemm_epi: qk_norm_eps must be >= 0");
+  }
   // LayerNorm / RMSNorm fold forms: launch_t's contract (gemm_impl.h), refused here with a message
   const bool fold_prod = a->ln_part_out != nullptr, fold_cons = a->ln_part_in != nullptr;
   const bool fold = fold_prod || fold_cons || a->hs_scale || a->hs_out || a->ln_u || a->ln_v || a->ln_rms || a->ln_nparts;
@@ -2541,6 +2614,9 @@ int f5h_op_gemm_epi(void* stream, const f5h_op_gemm_args* a, void* workspace, si
     g.v = compute ? vop : (void*)a->v;
     g.C = nullptr;
     g.ldc = 0;
+    g.q_norm_w = a->q_norm_w;
+    g.k_norm_w = a->k_norm_w;
+    g.qk_norm_eps = a->qk_norm_eps;
   }
   if (fold_prod) {
     // 0xFF bytes: NaN in fp32 and in both 16-bit types. Live rows: NaN with poison, else 0; guard rows: NaN
@@ -2573,6 +2649,24 @@ int f5h_op_gemm_epi(void* stream, const f5h_op_gemm_args* a, void* workspace, si
     HIPCK(op_to_f32(compute, kop, nqkv, a->k, st));
     HIPCK(op_to_f32(compute, vop, nqkv, a->v, st));
   }
+  return 0;
+}
+
+int f5h_op_text_upsample(void* stream, int32_t B, int32_t nt, int32_t N, int32_t td, const int64_t* text,
+                         const int32_t* seq_len, const float* in, float* out) {
+  if (B <= 0 || nt < 0 || N <= 0 || N > 8192 || td <= 0 || td % 4)
+    return fail(F5H_EINVAL, "op_text_upsample needs B > 0, nt >= 0, 0 < N <= 8192 and td % 4 == 0");
+  if ((nt > 0 && !text) || !in || !out || in == out) return fail(F5H_EINVAL, "op_text_upsample: null or aliased tensor");
+  TextUpArgs u{};
+  u.text = text;
+  u.B = B;
+  u.nt = nt;
+  u.N = N;
+  u.td = td;
+  u.seq_len = seq_len;
+  u.in_c = in;
+  u.out_c = out;
+  HIPCK(text_upsample(u, reinterpret_cast<hipStream_t>(stream)));
   return 0;
 }
 

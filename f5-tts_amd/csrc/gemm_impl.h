@@ -142,9 +142,15 @@ F5H_DEV bool tile_live(const GemmArgs& g, int m0, int BM) {
   return tile_live_rows(g.live_len, g.live_seq, g.M, m0, BM);
 }
 
+// qk_norm (defined with the 8-lane sums below)
+F5H_DEV V8 qk_norm8(V8 x, const V8& w, float eps, bool on);
+
 // Apply the epilogue to 8 consecutive columns [col, col+8) of output row `row`.
-template <typename TC, int EPI>
+// QKN (EPI_QKV, GemmArgs q_norm_w / k_norm_w): the head's RMSNorm on q and k, after the bias and before RoPE. The
+// callers' strips are 64 columns wide from a head start, so lanes 8i .. 8i + 7 hold one row's head (qk_norm8).
+template <typename TC, int EPI, bool QKN = false>
 F5H_DEV void epi8(const GemmArgs& g, int row, int col, V8 x, const V8* pre = nullptr) {
+  static_assert(!QKN || EPI == EPI_QKV, "qk_norm: the QKV epilogue");
   const bool full = col + 8 <= g.N;
   if (g.bias) {
     if (full) {
@@ -163,6 +169,7 @@ F5H_DEV void epi8(const GemmArgs& g, int row, int col, V8 x, const V8* pre = nul
     const int which = fdiv(col, inner), hc = col - which * inner;
     const int head = hc >> 6, dh = hc & 63;
     const int s = fdiv(row, g.seq_len), pos = row - s * g.seq_len;
+    if constexpr (QKN) x = qk_norm8(x, load8((which == 0 ? g.q_norm_w : g.k_norm_w) + dh), g.qk_norm_eps, which < 2);
     if (which < 2 && head < g.rope_heads) {
       const float4* cs = reinterpret_cast<const float4*>(g.rope + (int64_t)pos * 32 + (dh >> 1));
 #pragma unroll
@@ -320,6 +327,20 @@ F5H_DEV float sum8(float v) {
   v = add_nc(v, dpp8<0x4E>(v));
   return add_nc(v, dpp8<0x141>(v));
 }
+// qk_norm = "rms_norm" (modules.py:286-305, 493-496) on the 8 columns this lane holds of a head's 64; the row's other
+// 56 sit in the 7 neighbouring lanes of its group of 8 (the strip epilogue's layout with 64-column strips):
+// x rsqrt(mean(x^2) + eps) w in fp32 on the accumulators. Every rounding is written out and the sum's order fixed
+// (the lane's 8 in column order, then sum8's tree), so every tile configuration gives the same bits. on: q / k
+// columns (v passes through; a select, no branch).
+F5H_DEV V8 qk_norm8(V8 x, const V8& w, float eps, bool on) {
+  float s = mul_nc(x.v[0], x.v[0]);
+#pragma unroll
+  for (int e = 1; e < 8; ++e) s = add_nc(s, mul_nc(x.v[e], x.v[e]));
+  const float r = rsqrtf(add_nc(mul_nc(sum8(s), 1.f / 64.f), eps));
+#pragma unroll
+  for (int e = 0; e < 8; ++e) x.v[e] = on ? mul_nc(mul_nc(x.v[e], r), w.v[e]) : x.v[e];
+  return x;
+}
 // The LayerNorm fold's row statistics from 64-column strip partials (mean m_p, M2 q_p): mean = the mean of the strip
 // means, M2 = sum_p (q_p + 64 (m_p - mean)^2); a strip's term and the final rstd (LayerNorm eps 1e-6,
 // modules.py:316,336), each rounding explicit so the per-chunk-row form (LNF 2) and the once-per-row form
@@ -390,8 +411,10 @@ F5H_DEV void ln_row_stats(const GemmArgs& g, const u32x4 (&raw)[8], float* out) 
 // (EPI_GELU_TANH / EPI_QKV: the normalisation applied to the accumulators; 2 combines each row's strip partials
 // here, 3 reads the row's (mean, rstd) from ln_rows, which gemm_body filled from partials fetched before its K
 // loop); see GemmArgs.
+// QKN: qk_norm (GemmArgs q_norm_w / k_norm_w) on the q and k heads, after the bias and the fold consumer's
+// correction, before RoPE and the q scale; a compile-time choice, so the kernels without it keep their code.
 template <typename TC, int EPI, int MT, int NT, int WN, int EPAD, bool PREF, bool BIAS, int PM, int PT, int AUX = 0,
-          int PD = 1, int LNF = 0>
+          int PD = 1, int LNF = 0, bool QKN = false>
 F5H_DEV void epilogue_fast_t(const GemmArgs& g, const f32x4 (&acc)[MT][NT], float* Cs, int rbase, int cbase,
                              int lane, const V8 (&pre)[PM][PT], const float* ln_rows = nullptr) {
   constexpr bool LNCONS = LNF == 2 || LNF == 3;
@@ -401,6 +424,7 @@ F5H_DEV void epilogue_fast_t(const GemmArgs& g, const f32x4 (&acc)[MT][NT], floa
   static_assert(LNF == 0 || (WN == 64 && is16<TC>()), "the LayerNorm fold: 64-column wave strips, 16-bit operands");
   static_assert((LNF != 1 && LNF != 4) || EPI == EPI_RESID16, "fold producer: the 16-bit residual epilogue");
   static_assert(!LNCONS || EPI == EPI_GELU_TANH || EPI == EPI_QKV, "fold consumer: FFN1 or QKV");
+  static_assert(!QKN || (EPI == EPI_QKV && WN == 64), "qk_norm: QKV, a head per 64-column wave strip (8 lanes per row)");
   const int fr = lane & 15, q = lane >> 4;
   const int cc = lane % CH;
   const int col = cbase + cc * 8;
@@ -456,6 +480,10 @@ F5H_DEV void epilogue_fast_t(const GemmArgs& g, const f32x4 (&acc)[MT][NT], floa
     constexpr int OES = (EPI == EPI_STORE || EPI == EPI_RESID || EPI == EPI_INPROJ) ? 4 : (int)sizeof(TC);
     dst = rsrc_of(g.C, (uint64_t)(g.M + (EPI == EPI_INPROJ ? g.dual_rows : 0)) * g.ldc * OES);
   }
+  // qk_norm: the [64] gain of this wave's q or k head, the lane's 8 columns loaded once (a v wave loads k's, unused)
+  V8 qkw = V8{};
+  if constexpr (QKN) qkw = load8((which == 0 ? g.q_norm_w : g.k_norm_w) + dh);
+  const bool qkn_on = which < 2;
   // Loads only, raw bits, no arithmetic on their results here (see above): conversions happen at the
   // use, one strip later. Row indices are clamped instead of branched on (rows >= M are never stored).
   struct RowIn {
@@ -580,6 +608,7 @@ F5H_DEV void epilogue_fast_t(const GemmArgs& g, const f32x4 (&acc)[MT][NT], floa
 #pragma unroll
         for (int e = 0; e < 8; ++e) x.v[e] = add_nc(x.v[e], bias8.v[e]);
       }
+      if constexpr (QKN) x = qk_norm8(x, qkw, g.qk_norm_eps, qkn_on);
       if constexpr (EPI == EPI_QKV) {
         const V8 cs = as_v8(ri);
         // interleaved pairs (a, b) -> (a c - b s, b c + a s) as packed products and one packed add (each
@@ -687,7 +716,7 @@ F5H_DEV void epilogue_fast_t(const GemmArgs& g, const f32x4 (&acc)[MT][NT], floa
 }
 // FOLD: the fold forms are compiled in (not for the phase chain's kernels, which never run the fold)
 template <typename TC, int EPI, int MT, int NT, int WN, int EPAD, bool PREF, int AUX = 0, int PD = 1, bool FOLD = true,
-          int PM, int PT>
+          bool QKN = false, int PM, int PT>
 F5H_DEV void epilogue_fast(const GemmArgs& g, const f32x4 (&acc)[MT][NT], float* Cs, int rbase, int cbase,
                            int lane, const V8 (&pre)[PM][PT], const float* ln_rows = nullptr) {
   // LayerNorm fold forms (GemmArgs hs / ln_part_in: 16-bit, 64-column wave strips; bias always present there)
@@ -710,26 +739,26 @@ F5H_DEV void epilogue_fast(const GemmArgs& g, const f32x4 (&acc)[MT][NT], float*
     } else if constexpr (EPI == EPI_GELU_TANH || EPI == EPI_QKV) {
       if (g.ln_part_in && ln_rows) {
         if (g.bias)
-          epilogue_fast_t<TC, EPI, MT, NT, WN, EPAD, PREF, true, PM, PT, AUX, PD, 3>(g, acc, Cs, rbase, cbase, lane, pre,
+          epilogue_fast_t<TC, EPI, MT, NT, WN, EPAD, PREF, true, PM, PT, AUX, PD, 3, QKN>(g, acc, Cs, rbase, cbase, lane, pre,
                                                                                    ln_rows);
         else
-          epilogue_fast_t<TC, EPI, MT, NT, WN, EPAD, PREF, false, PM, PT, AUX, PD, 3>(g, acc, Cs, rbase, cbase, lane, pre,
+          epilogue_fast_t<TC, EPI, MT, NT, WN, EPAD, PREF, false, PM, PT, AUX, PD, 3, QKN>(g, acc, Cs, rbase, cbase, lane, pre,
                                                                                     ln_rows);
         return;
       }
       if (g.ln_part_in) {
         if (g.bias)
-          epilogue_fast_t<TC, EPI, MT, NT, WN, EPAD, PREF, true, PM, PT, AUX, PD, 2>(g, acc, Cs, rbase, cbase, lane, pre);
+          epilogue_fast_t<TC, EPI, MT, NT, WN, EPAD, PREF, true, PM, PT, AUX, PD, 2, QKN>(g, acc, Cs, rbase, cbase, lane, pre);
         else
-          epilogue_fast_t<TC, EPI, MT, NT, WN, EPAD, PREF, false, PM, PT, AUX, PD, 2>(g, acc, Cs, rbase, cbase, lane, pre);
+          epilogue_fast_t<TC, EPI, MT, NT, WN, EPAD, PREF, false, PM, PT, AUX, PD, 2, QKN>(g, acc, Cs, rbase, cbase, lane, pre);
         return;
       }
     }
   }
   if (g.bias)
-    epilogue_fast_t<TC, EPI, MT, NT, WN, EPAD, PREF, true, PM, PT, AUX, PD>(g, acc, Cs, rbase, cbase, lane, pre);
+    epilogue_fast_t<TC, EPI, MT, NT, WN, EPAD, PREF, true, PM, PT, AUX, PD, 0, QKN>(g, acc, Cs, rbase, cbase, lane, pre);
   else
-    epilogue_fast_t<TC, EPI, MT, NT, WN, EPAD, PREF, false, PM, PT, AUX, PD>(g, acc, Cs, rbase, cbase, lane, pre);
+    epilogue_fast_t<TC, EPI, MT, NT, WN, EPAD, PREF, false, PM, PT, AUX, PD, 0, QKN>(g, acc, Cs, rbase, cbase, lane, pre);
 }
 
 // Direct epilogue (round 5; the persistent kernel, whose LDS holds the operand ring only): the MFMAs run with swapped operands (W fragment as A, activation fragment as B),
@@ -960,7 +989,7 @@ F5H_DEV void epilogue_direct(const GemmArgs& g, const f32x4 (&acc)[MT][NT], int 
 // first operand load; blocks past the last tile (the chain pads each phase to whole XCD rounds) do nothing.
 // AUX: the cache policy of the strip epilogue's stores (kAuxWT: the write-through store policy, launch_cfg).
 template <typename TC, int EPI, int BM, int BN, int WGM, int WGN, int NS, bool FAST, int KB, bool PUB = false,
-          bool CHAIN = false, int AUX = 0>
+          bool CHAIN = false, int AUX = 0, bool QKN = false>
 F5H_DEV void gemm_body(const GemmArgs& g, const int b, const int nwg, uint4* lds, const ChainDep& dep) {
   const ProbeT probe_t = probe_enter(g.probe);
   typedef GemmCfg<BM, BN, WGM, WGN, NS, KB> C;
@@ -1214,11 +1243,12 @@ F5H_DEV void gemm_body(const GemmArgs& g, const int b, const int nwg, uint4* lds
   static_assert(FAST_EPI || !PUB, "the chain publishes after the fast (LDS-strip) epilogue");
   if constexpr (FAST_EPI) {
     static_assert(AUX == 0 || FAST_EPI, "the store policy exists for the strip epilogue only");
-    epilogue_fast<TC, EPI, MT, NT, WN, C::EPAD, PREF, PUB ? kAuxWT : AUX, 1, !PUB>(
+    epilogue_fast<TC, EPI, MT, NT, WN, C::EPAD, PREF, PUB ? kAuxWT : AUX, 1, !PUB, QKN>(
         g, acc, Cs, m0 + wm * WM, n0 + wn * WN, lane, pre, LNC ? ln_rows + 2 * wm * WM : nullptr);
     if constexpr (PUB) chain_publish(dep, g.M, m0, BM);
   }
   if constexpr (!FAST_EPI) {
+    static_assert(!QKN || WN == 64, "qk_norm in the general epilogue: 8 lanes per row of a 64-column strip");
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
       // swapped-operand layout: the lane's row fr, four consecutive columns 16j + 4q
@@ -1234,7 +1264,7 @@ F5H_DEV void gemm_body(const GemmArgs& g, const int b, const int nwg, uint4* lds
         const float* src = Cs + rr * C::EPAD + cc * 8;
         float4 a = *reinterpret_cast<const float4*>(src), b = *reinterpret_cast<const float4*>(src + 4);
         if (row < g.M && col < g.N)
-          epi8<TC, EPI>(g, row, col, V8{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}}, PREF ? &pre[PREF ? i : 0][PREF ? t : 0] : nullptr);
+          epi8<TC, EPI, QKN>(g, row, col, V8{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}}, PREF ? &pre[PREF ? i : 0][PREF ? t : 0] : nullptr);
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -1244,10 +1274,11 @@ F5H_DEV void gemm_body(const GemmArgs& g, const int b, const int nwg, uint4* lds
   probe_exit(g.probe, probe_t);
 }
 
-template <typename TC, int EPI, int BM, int BN, int WGM, int WGN, int NS, bool FAST = false, int KB = 128, int AUX = 0>
+template <typename TC, int EPI, int BM, int BN, int WGM, int WGN, int NS, bool FAST = false, int KB = 128, int AUX = 0,
+          bool QKN = false>
 __global__ __launch_bounds__(64 * WGM * WGN, 2) void gemm_kernel(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) uint4 lds[GemmCfg<BM, BN, WGM, WGN, NS, KB>::bytes / 16];
-  gemm_body<TC, EPI, BM, BN, WGM, WGN, NS, FAST, KB, false, false, AUX>(g, blockIdx.x, gridDim.x, lds, ChainDep{});
+  gemm_body<TC, EPI, BM, BN, WGM, WGN, NS, FAST, KB, false, false, AUX, QKN>(g, blockIdx.x, gridDim.x, lds, ChainDep{});
 }
 
 // ======================================================================================
@@ -1290,8 +1321,9 @@ struct PPCfg {
   static_assert(bytes <= 160 * 1024, "LDS");
 };
 
-template <typename TC, int EPI, int BM, int BN, int WGM2, int WGN2, int KS, int D, bool FAST = false>
+template <typename TC, int EPI, int BM, int BN, int WGM2, int WGN2, int KS, int D, bool FAST = false, bool QKN = false>
 __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmArgs g) {
+  static_assert(!QKN || FAST, "qk_norm in the ping-pong kernel: the strip epilogue only (launch_t re-routes the rest)");
   const ProbeT probe_t = probe_enter(g.probe);
   typedef PPCfg<BM, BN, WGM2, WGN2, KS, D> C;
   constexpr int WM = C::WM, WN = C::WN, MT = C::MT, NT = C::NT, NA = C::NA, NB = C::NB;
@@ -1460,8 +1492,8 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmArgs g) {
     // whole-column tiles: the strip-pipelined epilogue (the generic one below waits out every strip's
     // residual / RoPE loads before its stores: 13-15 us per 256x256 tile at C3, profiles/r03_timeline_c3.txt)
     const V8 none[1][1] = {};
-    epilogue_fast<TC, EPI, MT, NT, WN, C::EPAD, false>(g, acc, Cs, rbase, cbase, lane, none,
-                                                       LNC ? ln_rows + 2 * (grp * (BM / 2) + wm * WM) : nullptr);
+    epilogue_fast<TC, EPI, MT, NT, WN, C::EPAD, false, 0, 1, true, QKN>(
+        g, acc, Cs, rbase, cbase, lane, none, LNC ? ln_rows + 2 * (grp * (BM / 2) + wm * WM) : nullptr);
   } else {
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
@@ -1948,18 +1980,22 @@ static bool fast_epi_ok(const GemmArgs& a, int BN) {
          span < 0xF0000000ull;
 }
 
-template <typename TC, int EPI, int BM, int BN, int WGM2, int WGN2, int KS, int D>
+template <typename TC, int EPI, int BM, int BN, int WGM2, int WGN2, int KS, int D, bool QKN = false>
 static void launch_pp(const GemmArgs& a, hipStream_t st) {
   const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-  constexpr bool HOT = EPI == EPI_QKV || EPI == EPI_RESID || EPI == EPI_RESID16 || EPI == EPI_GELU_TANH ||
-                       EPI == EPI_GELU_ERF_OP || EPI == EPI_STORE || EPI == EPI_STORE16 || EPI == EPI_INPROJ;
-  if constexpr (HOT) {
-    if (fast_epi_ok<EPI>(a, BN)) {
-      hipLaunchKernelGGL((gemm_pp_kernel<TC, EPI, BM, BN, WGM2, WGN2, KS, D, true>), dim3(tiles), dim3(512), 0, st, a);
-      return;
+  if constexpr (QKN) {  // qk_norm: whole-column tiles only (launch_t sends the others to the 128x128 tile)
+    hipLaunchKernelGGL((gemm_pp_kernel<TC, EPI, BM, BN, WGM2, WGN2, KS, D, true, true>), dim3(tiles), dim3(512), 0, st, a);
+  } else {
+    constexpr bool HOT = EPI == EPI_QKV || EPI == EPI_RESID || EPI == EPI_RESID16 || EPI == EPI_GELU_TANH ||
+                         EPI == EPI_GELU_ERF_OP || EPI == EPI_STORE || EPI == EPI_STORE16 || EPI == EPI_INPROJ;
+    if constexpr (HOT) {
+      if (fast_epi_ok<EPI>(a, BN)) {
+        hipLaunchKernelGGL((gemm_pp_kernel<TC, EPI, BM, BN, WGM2, WGN2, KS, D, true>), dim3(tiles), dim3(512), 0, st, a);
+        return;
+      }
     }
+    hipLaunchKernelGGL((gemm_pp_kernel<TC, EPI, BM, BN, WGM2, WGN2, KS, D>), dim3(tiles), dim3(512), 0, st, a);
   }
-  hipLaunchKernelGGL((gemm_pp_kernel<TC, EPI, BM, BN, WGM2, WGN2, KS, D>), dim3(tiles), dim3(512), 0, st, a);
 }
 
 // cfg 13: one persistent block per CU (whole-column tiles with the direct epilogue; others take cfg 11)
@@ -2005,7 +2041,7 @@ static void launch_8p(const GemmArgs& a, hipStream_t st) {
   hipLaunchKernelGGL((gemm_8p_kernel<TC, EPI>), dim3(tiles), dim3(512), 0, st, a);
 }
 
-template <typename TC, int EPI, int BM, int BN, int WGM, int WGN, int NS, int KB = 128>
+template <typename TC, int EPI, int BM, int BN, int WGM, int WGN, int NS, int KB = 128, bool QKN = false>
 static void launch_cfg(const GemmArgs& a, hipStream_t st) {
   const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
   constexpr bool HOT = EPI == EPI_QKV || EPI == EPI_RESID || EPI == EPI_RESID16 || EPI == EPI_GELU_TANH ||
@@ -2019,18 +2055,40 @@ static void launch_cfg(const GemmArgs& a, hipStream_t st) {
       // cost their consumers the lines the plain stores leave in the XCD's L2.
       if constexpr (store_wt_epi<TC, EPI>()) {
         if (a.store_wt) {
-          hipLaunchKernelGGL((gemm_kernel<TC, EPI, BM, BN, WGM, WGN, NS, true, KB, kAuxWT>), dim3(tiles),
+          hipLaunchKernelGGL((gemm_kernel<TC, EPI, BM, BN, WGM, WGN, NS, true, KB, kAuxWT, QKN>), dim3(tiles),
                              dim3(64 * WGM * WGN), 0, st, a);
           return;
         }
       }
-      hipLaunchKernelGGL((gemm_kernel<TC, EPI, BM, BN, WGM, WGN, NS, true, KB>), dim3(tiles), dim3(64 * WGM * WGN), 0,
-                         st, a);
+      hipLaunchKernelGGL((gemm_kernel<TC, EPI, BM, BN, WGM, WGN, NS, true, KB, 0, QKN>), dim3(tiles),
+                         dim3(64 * WGM * WGN), 0, st, a);
       return;
     }
   }
-  hipLaunchKernelGGL((gemm_kernel<TC, EPI, BM, BN, WGM, WGN, NS, false, KB>), dim3(tiles), dim3(64 * WGM * WGN), 0, st,
-                     a);
+  hipLaunchKernelGGL((gemm_kernel<TC, EPI, BM, BN, WGM, WGN, NS, false, KB, 0, QKN>), dim3(tiles), dim3(64 * WGM * WGN),
+                     0, st, a);
+}
+
+// QKV launches with qk_norm (GemmArgs q_norm_w / k_norm_w): the kernels with the norm compiled into their epilogue,
+// instantiated in translation units of their own (gemm_qkn_*.hip). cfg: 0, 1, 5, or 11 with whole 256-column tiles.
+hipError_t gemm_launch_qkn_bf16(const GemmArgs& a, int cfg, hipStream_t st);
+hipError_t gemm_launch_qkn_f16(const GemmArgs& a, int cfg, hipStream_t st);
+hipError_t gemm_launch_qkn_f32(const GemmArgs& a, int cfg, hipStream_t st);
+template <typename TC>
+static hipError_t launch_qkn(const GemmArgs& a, int cfg, hipStream_t st) {
+  if constexpr (is16<TC>()) {
+    switch (cfg) {
+      case 0: launch_cfg<TC, EPI_QKV, 64, 128, 2, 2, 3, 128, true>(a, st); break;
+      case 1: launch_cfg<TC, EPI_QKV, 128, 128, 2, 2, 2, 128, true>(a, st); break;
+      case 5: launch_cfg<TC, EPI_QKV, 192, 128, 2, 2, 2, 128, true>(a, st); break;
+      case 11: launch_pp<TC, EPI_QKV, 256, 256, 1, 4, 1, 3, true>(a, st); break;
+      default: return hipErrorInvalidValue;
+    }
+  } else {  // the fp32 parity mode always uses cfg 0
+    if (cfg != 0) return hipErrorInvalidValue;
+    launch_cfg<TC, EPI_QKV, 64, 128, 2, 2, 3, 128, true>(a, st);
+  }
+  return hipGetLastError();
 }
 
 template <typename TC, int EPI>
@@ -2042,9 +2100,16 @@ static hipError_t launch_t(const GemmArgs& a, hipStream_t st) {
   // 256x256 configuration without it (12: 32-column quadrant strips, 13: register-only epilogue) runs as cfg 11, the
   // same tile (every configuration gives the same bits); anything else is refused rather than ignored (the results
   // would be those of an unnormalised operand)
-  if ((a.ln_part || a.ln_part_in) && (cfg == 12 || cfg == 13)) cfg = 11;
+  // qk_norm (q_norm_w / k_norm_w, EPI_QKV only) lives in the same epilogues — the strip epilogue and, for the
+  // 64x128 / 128x128 / 192x128 tiles, the general one — and is re-routed the same way; a request no route honours is
+  // refused, never stored un-normed
+  const bool qkn = a.q_norm_w || a.k_norm_w;
+  if (qkn && (EPI != EPI_QKV || !a.q_norm_w || !a.k_norm_w || a.heads <= 0 || a.N != 3 * a.heads * 64))
+    return hipErrorInvalidValue;
+  const bool strips = a.ln_part || a.ln_part_in || qkn;
+  if (strips && (cfg == 12 || cfg == 13)) cfg = 11;
   // a 256x256 tile needs whole 256-column tiles for the strip epilogue: narrower outputs take the 128x128 tile
-  if ((a.ln_part || a.ln_part_in) && cfg == 11 && !fast_epi_ok<EPI>(a, 256)) cfg = 1;
+  if (strips && cfg == 11 && (!fast_epi_ok<EPI>(a, 256) || a.K % 64)) cfg = 1;
   if (a.hs || a.ln_part || a.ln_part_in) {
     // LayerNorm form: producer hs + hs_scale, consumer u + v; RMSNorm form (ln_rms): neither. Row masks only with the
     // RMSNorm form (the DiT fold runs on unmasked rows; UNetT batches keep their masks), never the pad-row skip (a
@@ -2057,6 +2122,14 @@ static hipError_t launch_t(const GemmArgs& a, hipStream_t st) {
         (cfg != 0 && cfg != 1 && cfg != 5 && cfg != 11) || !fast_epi_ok<EPI>(a, bn) || (a.rowkeep && !a.ln_rms) ||
         a.live_len)
       return hipErrorInvalidValue;
+  }
+  if constexpr (EPI == EPI_QKV) {
+    if (qkn) {
+      if (cfg != 0 && cfg != 1 && cfg != 5 && cfg != 11) return hipErrorInvalidValue;
+      if constexpr (std::is_same<TC, bf16>::value) return gemm_launch_qkn_bf16(a, cfg, st);
+      else if constexpr (std::is_same<TC, float>::value) return gemm_launch_qkn_f32(a, cfg, st);
+      else return gemm_launch_qkn_f16(a, cfg, st);
+    }
   }
   switch (cfg) {
     case 0: launch_cfg<TC, EPI, 64, 128, 2, 2, 3>(a, st); break;

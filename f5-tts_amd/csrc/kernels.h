@@ -42,10 +42,15 @@ struct DevProbe {
 };
 constexpr int kTimelineWG = 8192;  // workgroups recorded per timeline
 
+// Layout: a kernel argument of every GEMM launch. Its 4-byte fields sit where alignment padding would otherwise be
+// (k_split, store_wt, qk_norm_eps away from the fields they go with), so that the struct stays 304 bytes: 24 bytes
+// more moved the hidden grid-size argument the kernels read at entry onto another cache line of the kernarg segment
+// and measured C2 -0.4 % with unchanged kernel code.
 struct GemmArgs {
   const void* A; int64_t lda;      // [M,K] row-major, TA elements
   const void* W; int64_t ldw;      // [Npad,K] row-major, operand elements (rows padded to 128)
   int M, N, K;                     // K: multiple of 64 (bf16) / 32 (fp32)
+  int k_split;                     // with A2 (below)
   const float* bias;               // [N] or null
   void* C; int64_t ldc;            // output
   const float* gate;               // EPI_RESID: [N] or null (=1)
@@ -56,11 +61,14 @@ struct GemmArgs {
   const float2* rope;              // [L][32] (cos, sin)
   int seq_len;                     // L: rows per sequence
   int heads, rope_heads;
+  int store_wt;                    // store policy (below)
   void* q; void* k; void* v;
   float q_scale;                   // EPI_QKV: q is stored pre-multiplied by this (0 -> 1)
+  float qk_norm_eps;               // qk_norm (below)
   DevProbe probe;                  // in-kernel launch timing (null slots: off)
   const void* resid;               // EPI_RESID / EPI_RESID16 residual input (null: C)
-  const void* A2; int k_split;     // A columns [k_split, K) come from A2 (same lda), e.g. cat(x, skip)
+  const void* A2;                  // A columns [k_split, K) come from A2 (same lda), e.g. cat(x, skip)
+  const float* q_norm_w;           // qk_norm (below)
   // EPI_RESID / EPI_RESID16 with rowkeep: the live rows of sequence s are [s*live_seq, s*live_seq +
   // live_len[s]); a tile with no live row skips its K loop and epilogue (its rows keep the residual, as
   // the masked rows of a computed tile do). Null: every tile is computed.
@@ -83,9 +91,17 @@ struct GemmArgs {
   int ln_rms; float ln_eps;
   // Store policy: 1 = the epilogue's stores are write-through (sc1) where the launch has such a variant
   // (EPI_QKV / EPI_RESID16 / EPI_GELU_TANH in the 16-bit 64x128, 128x128 and 192x128 kernels), 0 = plain stores.
-  // Same values either way. Set from gemm_store_wt (DESIGN.md §3 'Launch boundaries').
-  int store_wt;
+  // Same values either way. Set from gemm_store_wt (DESIGN.md §3 'Launch boundaries'). (store_wt: above)
+  // EPI_QKV with qk_norm = "rms_norm" (modules.py:286-305, 493-496): both set, or both null (no norm). Per row and
+  // head, q <- q rsqrt(mean(q^2) + qk_norm_eps) q_norm_w and k likewise with k_norm_w (each [64] fp32, shared by the
+  // heads; the mean over the head's 64 channels), in fp32 on the accumulators after the bias and the fold consumer's
+  // correction, before RoPE and q_scale, on every head (also those rope_heads leaves unrotated); v is untouched.
+  // Kernels with the norm are instantiations of their own (gemm_impl.h QKN): launches without it run the same code
+  // as before. Tile configurations 12 and 13 have no such kernel and run as 11 (or 1), with the same bits.
+  // (q_norm_w, qk_norm_eps: above)
+  const float* k_norm_w;
 };
+static_assert(sizeof(GemmArgs) == 304, "GemmArgs: keep the kernel argument's size (see the layout note)");
 
 // Does the row tile [m0, m0 + BM) of an M-row GEMM hold a live row? Sequence s (rows [s*live_seq, (s+1)*live_seq))
 // contributes the tile's rows [max(m0, r0), min(last + 1, r0 + live_seq)); its live rows are [r0, r0 +
@@ -180,6 +196,19 @@ struct TextEmbArgs {
   uint8_t* keep;                // [2B*N] !fill (for masked_fill after each block) or null
 };
 hipError_t text_embed(const TextEmbArgs& a, hipStream_t st);
+// text_embedding_average_upsampling (TextEmbedding.average_upsample_text_by_mask, dit.py:55-84): per sequence, the T
+// valid tokens (not filler after the +1 shift and the per-sample valid range; the mask precedes drop_text, so both
+// branches share it; not necessarily a prefix) are spread over the first audio_len = seq_len[b] (N when null) frames:
+// with base = audio_len / T and rem = audio_len % T the first T - rem tokens repeat base times, the last rem tokens
+// base + 1 times; frames past audio_len, and every frame when T == 0, are zero. A gather (bitwise). in / out:
+// [B, N, td] fp32 each, distinct buffers; the _u pair (the unconditional branch) may be null. N <= 8192, td % 4 == 0.
+struct TextUpArgs {
+  const int64_t* text; int B, nt, N, td;
+  const int32_t* seq_len;
+  const float* in_c; const float* in_u;
+  float* out_c; float* out_u;
+};
+hipError_t text_upsample(const TextUpArgs& a, hipStream_t st);
 // depthwise conv k7 pad3 + bias then LayerNorm(affine, eps 1e-6) -> operand dtype. x: [S, L, C] fp32
 hipError_t dwconv_ln(int compute, const float* x, int S, int L, int C, const float* dw_w, const float* dw_b,
                      const float* ln_w, const float* ln_b, void* out, hipStream_t st);

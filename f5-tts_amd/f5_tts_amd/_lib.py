@@ -62,6 +62,7 @@ EXPORTS = (
     "f5h_op_dwconv_ln",
     "f5h_op_grn",
     "f5h_op_gemm_epi",
+    "f5h_op_text_upsample",
     "f5h_op_lnfold_uv",
     "f5h_op_scale_cols",
     "f5h_gemm_force_config",
@@ -85,7 +86,9 @@ KCLASS = {"ffn1": 0, "attention": 1, "qkv": 2, "ffn2": 3, "conv": 4, "out": 5, "
 class Arch(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in (
         "backbone", "dim", "depth", "heads", "dim_head", "ff_dim", "text_dim", "text_num_embeds", "mel_dim",
-        "conv_layers", "text_mask_padding", "pe_attn_head", "attn_mask_enabled", "compute")]
+        "conv_layers", "text_mask_padding", "pe_attn_head", "attn_mask_enabled", "compute",
+        # appended options: read by a library that exports f5h_op_text_upsample (has_dit_options)
+        "qk_norm", "long_skip_connection", "text_average_upsampling")]
 
 
 class VocosArch(ctypes.Structure):
@@ -143,6 +146,8 @@ class OpGemmArgs(ctypes.Structure):
         ("ln_part_in", ctypes.c_void_p), ("ln_u", ctypes.c_void_p), ("ln_v", ctypes.c_void_p),
         ("ln_nparts", ctypes.c_int32), ("ln_rms", ctypes.c_int32), ("ln_eps", ctypes.c_float),
         ("poison", ctypes.c_int32),
+        # qk_norm (both null: none)
+        ("q_norm_w", ctypes.c_void_p), ("k_norm_w", ctypes.c_void_p), ("qk_norm_eps", ctypes.c_float),
     ]
 
 
@@ -231,6 +236,9 @@ def lib():
             L.f5h_op_lnfold_uv.restype = ctypes.c_int
             L.f5h_op_scale_cols.argtypes = [vp, i32, i64, i32, vp, vp, vp, vp, sz]
             L.f5h_op_scale_cols.restype = ctypes.c_int
+    if hasattr(L, "f5h_op_text_upsample"):  # absent from an older build (has_dit_options)
+        L.f5h_op_text_upsample.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp]
+        L.f5h_op_text_upsample.restype = ctypes.c_int
     L.f5h_gemm_force_config.argtypes = [i32]
     L.f5h_gemm_force_config.restype = ctypes.c_int
     # test hooks: bound when present, so an older build loaded through F5H_LIB (one-box A/Bs) still loads
@@ -287,6 +295,12 @@ def lib():
 def has_ode() -> bool:
     """False for an older build (F5H_LIB) without f5h_sample_ode: such a library samples with Euler only."""
     return hasattr(lib(), "f5h_sample_ode")
+
+
+def has_dit_options() -> bool:
+    """False for an older build (F5H_LIB) without f5h_op_text_upsample: such a library ignores the arch fields
+    qk_norm / long_skip_connection / text_average_upsampling and the qk_norm fields of the GEMM op hook."""
+    return hasattr(lib(), "f5h_op_text_upsample")
 
 
 def check(rc: int, what: str = "f5h"):

@@ -132,6 +132,9 @@ def param_shapes(arch: dict) -> "dict[str, tuple]":
             s[p + f"{n}.bias"] = (inner,)
         s[p + "to_out.0.weight"] = (d, inner)
         s[p + "to_out.0.bias"] = (d,)
+        if arch.get("qk_norm"):  # RMSNorm(dim_head) gains shared by the heads (modules.py:402-407)
+            s[p + "q_norm.weight"] = (Dh,)
+            s[p + "k_norm.weight"] = (Dh,)
 
     def ff(p):
         s[p + "ff.0.0.weight"] = (F, d)
@@ -146,6 +149,8 @@ def param_shapes(arch: dict) -> "dict[str, tuple]":
             s[p + "attn_norm.linear.bias"] = (6 * d,)
             attn(p + "attn.")
             ff(p + "ff.")
+        if arch.get("long_skip_connection"):
+            s["long_skip_connection.weight"] = (d, 2 * d)  # nn.Linear(2d, d, bias=False) (dit.py:228)
         s["norm_out.linear.weight"] = (2 * d, d)
         s["norm_out.linear.bias"] = (2 * d,)
     elif arch["backbone"] == "UNetT":

@@ -31,10 +31,18 @@ def _arch_struct(arch: dict, compute: str) -> _lib.Arch:
     a.pe_attn_head = int(arch.get("pe_attn_head") or 0)
     a.attn_mask_enabled = int(bool(arch.get("attn_mask_enabled", False)))
     a.compute = _lib.COMPUTE[compute]
-    if arch.get("qk_norm"):
-        raise NotImplementedError("qk_norm is not used by any shipped config (F5TTS_*.yaml qk_norm: null)")
-    if arch.get("long_skip_connection") or arch.get("text_embedding_average_upsampling"):
-        raise NotImplementedError("long_skip_connection / average upsampling are off in every shipped config")
+    qk_norm = arch.get("qk_norm")
+    if qk_norm not in (None, "rms_norm"):
+        raise ValueError(f"Unimplemented qk_norm: {qk_norm}")  # as modules.py:408-409
+    dit = arch["backbone"] == "DiT"
+    a.qk_norm = 1 if qk_norm else 0
+    a.long_skip_connection = int(bool(dit and arch.get("long_skip_connection")))
+    a.text_average_upsampling = int(bool(dit and arch.get("text_embedding_average_upsampling")))
+    if a.text_average_upsampling:
+        assert a.text_mask_padding, "text_embedding_average_upsampling requires text_mask_padding to be True"
+    if (a.qk_norm or a.long_skip_connection or a.text_average_upsampling) and not _lib.has_dit_options():
+        raise RuntimeError("the loaded libf5h.so has no f5h_op_text_upsample (an older build): it would ignore qk_norm, "
+                           "long_skip_connection and text_embedding_average_upsampling")
     return a
 
 
@@ -429,7 +437,8 @@ EPI = {"store": 0, "silu": 1, "gelu_tanh": 2, "gelu_erf": 3, "resid": 4, "resid_
 def op_gemm_epi(epi, A, W, bias=None, C=None, compute="bf16", A2=None, k_split=0, resid=None, gate=None, rowkeep=None,
                 live_len=None, live_seq=0, add=None, dual_rows=0, seq_len=0, heads=0, rope_heads=0, q_scale=0.0,
                 hs_scale=None, ln_producer=False, ln_part_in=None, ln_u=None, ln_v=None, ln_rms=False, ln_eps=0.0,
-                ln_nparts=None, poison=False, ws_fill=None, return_ws=False):
+                ln_nparts=None, poison=False, ws_fill=None, return_ws=False, q_norm_w=None, k_norm_w=None,
+                qk_norm_eps=1e-6):
     """A GEMM with epilogue `epi` (a key of EPI; f5h_op_gemm_epi). The in/out epilogues update a copy of C and
     return it; "inproj" returns C [M + dual_rows, N]; "qkv" returns (q, k, v [S,H,L,64], rope [L,32,2]).
 
@@ -440,7 +449,8 @@ def op_gemm_epi(epi, A, W, bias=None, C=None, compute="bf16", A2=None, k_split=0
     form) or ln_rms, and the variance epsilon ln_eps. ln_nparts overrides the strip count (validation tests).
     ws_fill: byte the workspace is filled with before the call; return_ws: the workspace is appended to the result
     (its buffers are taken in f5h_op_gemm_epi's order, each from a multiple of 256 bytes; the bytes past the last one
-    are never written)."""
+    are never written). q_norm_w, k_norm_w [64] ("qkv"): qk_norm = "rms_norm" with epsilon qk_norm_eps, the RMSNorm
+    of every q / k head after the bias and ahead of RoPE; both None: no norm."""
     M, K = A.shape
     N = W.shape[0]
     dev = A.device
@@ -477,6 +487,11 @@ def op_gemm_epi(epi, A, W, bias=None, C=None, compute="bf16", A2=None, k_split=0
         rope = torch.empty(max(seq_len, 0), 32, 2, dtype=torch.float32, device=dev)
         a.seq_len, a.heads, a.rope_heads, a.q_scale = int(seq_len), int(heads), int(rope_heads), float(q_scale)
         a.q, a.k, a.v, a.rope_out = q.data_ptr(), k.data_ptr(), v.data_ptr(), rope.data_ptr()
+        if q_norm_w is not None or k_norm_w is not None:
+            if not _lib.has_dit_options():
+                raise RuntimeError("the loaded libf5h.so has no qk_norm (an older build)")
+            q_norm_w, k_norm_w = _f32(q_norm_w, dev), _f32(k_norm_w, dev)
+            a.q_norm_w, a.k_norm_w, a.qk_norm_eps = _lib.ptr(q_norm_w), _lib.ptr(k_norm_w), float(qk_norm_eps)
         ws_bytes += max(seq_len, 0) * 256 + 1024
         out = (q, k, v, rope)
     else:
@@ -493,6 +508,21 @@ def op_gemm_epi(epi, A, W, bias=None, C=None, compute="bf16", A2=None, k_split=0
                "f5h_op_gemm_epi")
     res = (out, hs, parts) if ln_producer else out
     return (res, ws) if return_ws else res
+
+
+def op_text_upsample(te, text, seq_len=None, out=None):
+    """average_upsample_text_by_mask alone (f5h_op_text_upsample): te [B,N,td] fp32, text [B,nt] int64 (-1 = padding),
+    seq_len [B] or None (= N). Returns `out` (a fresh [B,N,td] of NaN when None) with every row written."""
+    B, N, td = te.shape
+    dev = te.device
+    te = _f32(te)
+    text = text.to(dev, torch.int64).contiguous()
+    sl = None if seq_len is None else seq_len.to(dev, torch.int32).contiguous()
+    if out is None:
+        out = torch.full((B, N, td), float("nan"), dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().f5h_op_text_upsample(_lib.stream_handle(dev), B, text.shape[1], N, td, text.data_ptr(),
+                                               _lib.ptr(sl), te.data_ptr(), out.data_ptr()), "f5h_op_text_upsample")
+    return out
 
 
 def op_lnfold_uv(table, W1, Wqkv, nfe, out_off, compute="bf16"):

@@ -47,6 +47,11 @@ class EngineBackbone(nn.Module):
 
     def _setup(self, arch: dict):
         self.arch = configs.get_arch(arch)
+        if self.arch.get("qk_norm") not in (None, "rms_norm"):  # Attention.__init__ (modules.py:402-409)
+            raise ValueError(f"Unimplemented qk_norm: {self.arch['qk_norm']}")
+        if self.arch.get("text_embedding_average_upsampling"):  # TextEmbedding.__init__ (dit.py:42-43)
+            assert self.arch["text_mask_padding"], \
+                "text_embedding_average_upsampling requires text_mask_padding to be True"
         self.dim = self.arch["dim"]
         self.depth = self.arch["depth"]
         build_param_tree(self, configs.param_shapes(self.arch))

@@ -64,6 +64,17 @@ typedef struct f5h_arch {
   int32_t pe_attn_head;      /* 0 = rope on all heads, k>0 = first k heads (modules.py:503-506) */
   int32_t attn_mask_enabled; /* 0/1: key-padding mask in attention (modules.py:512-516) */
   int32_t compute;           /* f5h_compute: FP32 parity mode, BF16 or FP16 MFMA mode */
+  /* Appended options (all 0: none; a library that exports f5h_op_text_upsample reads them):
+   * qk_norm: 0 none, 1 "rms_norm" (modules.py:402-407, 493-496): RMSNorm(dim_head, eps 1e-6) of every q and k head
+   *   ahead of RoPE, fused into the QKV GEMM's epilogue in fp32 on the accumulators (the 16-bit modes round once, at
+   *   the store); parameters {attn}.q_norm.weight / {attn}.k_norm.weight [64], DiT and UNetT.
+   * long_skip_connection (DiT, dit.py:228, 354-365): x = W . cat(x, input embedding) after the last block, ahead of
+   *   the final AdaLN; parameter long_skip_connection.weight [d, 2d].
+   * text_average_upsampling (DiT, needs text_mask_padding; dit.py:55-84, 131-137): the valid text tokens' embeddings
+   *   spread evenly over each sequence's frames at the end of the text embedding. */
+  int32_t qk_norm;
+  int32_t long_skip_connection;
+  int32_t text_average_upsampling;
 } f5h_arch;
 
 /* One named parameter, host memory, float32, C-contiguous, with the reference's
@@ -404,9 +415,22 @@ typedef struct f5h_op_gemm_args {
   int32_t ln_nparts, ln_rms;
   float ln_eps;
   int32_t poison;
+  /* qk_norm (epi 7; both NULL: none): q <- q rsqrt(mean_64(q^2) + qk_norm_eps) q_norm_w per row and head, k likewise
+   * with k_norm_w ([64] each), after the bias (and the fold consumer's correction), before RoPE and q_scale, on every
+   * head; v is untouched. Every tile configuration gives the same bits (12 and 13 run as 11 or 1). */
+  const float* q_norm_w;
+  const float* k_norm_w;
+  float qk_norm_eps;
 } f5h_op_gemm_args;
 #define F5H_OP_GUARD_ROWS 4
 int f5h_op_gemm_epi(void* stream, const f5h_op_gemm_args* args, void* workspace, size_t workspace_bytes);
+/* The text average upsampling kernel alone (text_average_upsampling): text [B, nt] token ids (-1 = padding),
+ * seq_len [B] or NULL (= N): each sequence's frames; in, out [B, N, td] fp32, distinct. Valid tokens are those with
+ * id != -1 at positions below min(nt, seq_len[b]); with T of them, base = seq_len / T and rem = seq_len % T, the first
+ * T - rem repeat base times and the last rem repeat base + 1 times over frames [0, seq_len); later frames, and all of
+ * them when T == 0, are zero. N <= 8192, td % 4 == 0. */
+int f5h_op_text_upsample(void* stream, int32_t B, int32_t nt, int32_t N, int32_t td, const int64_t* text,
+                         const int32_t* seq_len, const float* in, float* out);
 /* lnfold_uv alone (16-bit modes): table [rows, stride] fp32 holds, per ODE step s < nfe, the AdaLN modulation rows
  * of `depth` layers ([depth][6][d]: shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp) in its first
  * 6 d depth floats; the kernel writes, per step and layer l, at column out_off + l (2F + 6d): u1 [F], v1 [F] (FFN1,
