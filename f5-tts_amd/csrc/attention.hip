@@ -464,7 +464,12 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
   // permlane32 swap per dword pairs groups k and k+1, so every lane stores 16 contiguous bytes
   // (lower lanes group k, upper lanes group k+1): 4 dwordx4 stores instead of 8 dwordx2
   if (!wave_dead) {
-    T* O = reinterpret_cast<T*>(a.o) + (((int64_t)s_idx * L + min(qrow, L - 1)) * a.H + head) * 64;
+    // split output (AttnArgs::o_split): rows below sp of o [S, sp, H*64], the others of o2 [S, L - sp, H*64]; a wave's
+    // 32 rows may straddle sp, so the plain form picks each lane's row pointer (sp = L without a split: always o)
+    const int sp = a.o_split > 0 ? a.o_split : L;
+    const int orow = min(qrow, L - 1);
+    T* O = orow < sp ? reinterpret_cast<T*>(a.o) + (((int64_t)s_idx * sp + orow) * a.H + head) * 64
+                     : reinterpret_cast<T*>(a.o2) + (((int64_t)s_idx * (L - sp) + (orow - sp)) * a.H + head) * 64;
     // WT: the wave's staging tile, 32 rows x 128 B past the first 4 KB of the ring (the vote flags live there;
     // all reads of the K/V tiles have retired, see above), chunk c of row r at c ^ (r & 7)
     uint4* const stg = lds + 256 + wid * 256;
@@ -493,14 +498,33 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
       // the (sequence, head)'s O columns as a buffer: rows past L fall outside its extent and are dropped by the
       // range check (the plain form's qrow < L); wave-uniform base, so the descriptor sits in scalar registers
       const int64_t rstride = (int64_t)a.H * 64 * sizeof(T);
-      const __amdgpu_buffer_rsrc_t ors = rsrc_of(reinterpret_cast<T*>(a.o) + ((int64_t)s_idx * L * a.H + head) * 64,
-                                                 (uint64_t)(L - 1) * rstride + 64 * sizeof(T));
+      // (split output: the descriptor ends at row sp, which drops the wave's rows of the second part)
+      const int sps = __builtin_amdgcn_readfirstlane(sp);
+      const __amdgpu_buffer_rsrc_t ors = rsrc_of(reinterpret_cast<T*>(a.o) + ((int64_t)s_idx * sps * a.H + head) * 64,
+                                                 (uint64_t)(sps - 1) * rstride + 64 * sizeof(T));
       const int row0 = qb * (32 * NW) + wid_s * 32;
+      if (row0 < sps) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int r = i * 8 + (lane >> 3), c = lane & 7;
-        const uint4 w = stg[r * 8 + (c ^ (r & 7))];
-        buffer_store16<kAuxWT>(ors, (uint32_t)((row0 + r) * rstride + c * 16), __builtin_bit_cast(u32x4, w));
+        for (int i = 0; i < 4; ++i) {
+          const int r = i * 8 + (lane >> 3), c = lane & 7;
+          const uint4 w = stg[r * 8 + (c ^ (r & 7))];
+          buffer_store16<kAuxWT>(ors, (uint32_t)((row0 + r) * rstride + c * 16), __builtin_bit_cast(u32x4, w));
+        }
+      }
+      if (sps < L && row0 + 32 > sps) {
+        // the wave's rows from sp on, through a descriptor of their own over o2's (sequence, head) columns; rows
+        // below sp get an offset past every extent (attn_wt_ok keeps real offsets below 2^31)
+        const __amdgpu_buffer_rsrc_t ors2 =
+            rsrc_of(reinterpret_cast<T*>(a.o2) + ((int64_t)s_idx * (L - sps) * a.H + head) * 64,
+                    (uint64_t)(L - sps - 1) * rstride + 64 * sizeof(T));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int r = i * 8 + (lane >> 3), c = lane & 7;
+          const uint4 w = stg[r * 8 + (c ^ (r & 7))];
+          const int r2 = row0 + r - sps;
+          buffer_store16<kAuxWT>(ors2, r2 >= 0 ? (uint32_t)(r2 * rstride + c * 16) : 0x80000000u,
+                                 __builtin_bit_cast(u32x4, w));
+        }
       }
     }
   }
@@ -566,7 +590,9 @@ __global__ __launch_bounds__(64) void attn_f32_kernel(AttnArgs a) {
     }
   }
   if (qrow < L) {
-    float* O = reinterpret_cast<float*>(a.o) + (((int64_t)s_idx * L + qrow) * a.H + head) * 64;
+    const int sp = a.o_split > 0 ? a.o_split : L;  // split output (AttnArgs::o_split)
+    float* O = qrow < sp ? reinterpret_cast<float*>(a.o) + (((int64_t)s_idx * sp + qrow) * a.H + head) * 64
+                         : reinterpret_cast<float*>(a.o2) + (((int64_t)s_idx * (L - sp) + (qrow - sp)) * a.H + head) * 64;
     const float inv = 1.f / l_run;
 #pragma unroll
     for (int d = 0; d < 64; ++d) O[d] = o[d] * inv;
@@ -613,6 +639,7 @@ int attention_store_wt(int compute, const AttnArgs& a, int want) {
 
 hipError_t attention(int compute, const AttnArgs& a0, hipStream_t st) {
   if (a0.S <= 0 || a0.H <= 0 || a0.L <= 0) return hipErrorInvalidValue;
+  if (a0.o_split < 0 || a0.o_split >= a0.L || (a0.o_split > 0 && !a0.o2)) return hipErrorInvalidValue;
   AttnArgs a = a0;
   a.force_safe = g_force_safe;
   if (store_policy_forced() >= 0) a.store_wt = attention_store_wt(compute, a0, store_policy_forced());

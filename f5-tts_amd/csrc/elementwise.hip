@@ -481,7 +481,8 @@ __global__ void text_embed_kernel(TextEmbArgs a) {
     float ec = valid ? a.table[(int64_t)tok * a.td + c] : 0.f;
     float eu = valid ? a.table[c] : 0.f;  // drop_text -> id 0
     if (a.freqs) {
-      float f = valid ? a.freqs[(int64_t)n * a.td + c] : 0.f;
+      const int fr = a.freq_rows > 0 ? min(n, a.freq_rows - 1) : n;  // get_pos_embed_indices' clamp (MMDiT table)
+      float f = valid ? a.freqs[(int64_t)fr * a.td + c] : 0.f;
       ec += f;
       eu += f;
     }
@@ -905,6 +906,16 @@ __global__ void rowkeep_kernel(const int32_t* dur, int B, int S, int L, int off,
 }
 hipError_t build_rowkeep(const int32_t* dur, int B, int S, int L, int off, uint8_t* keep, hipStream_t st) {
   hipLaunchKernelGGL(rowkeep_kernel, dim3(nblk((int64_t)S * L, 256)), dim3(256), 0, st, dur, B, S, L, off, keep);
+  return hipGetLastError();
+}
+__global__ void textkeep_kernel(const int64_t* text, int B, int S, int nt, uint8_t* keep) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)S * nt) return;
+  const int s = (int)(i / nt), j = (int)(i - (int64_t)s * nt);
+  keep[i] = text[(int64_t)(s % B) * nt + j] != -1 ? 1 : 0;
+}
+hipError_t build_textkeep(const int64_t* text, int B, int S, int nt, uint8_t* keep, hipStream_t st) {
+  hipLaunchKernelGGL(textkeep_kernel, dim3(nblk((int64_t)S * nt, 256)), dim3(256), 0, st, text, B, S, nt, keep);
   return hipGetLastError();
 }
 __global__ void kvlen_kernel(const int32_t* dur, int B, int S, int off, int32_t* kv) {

@@ -67,20 +67,35 @@ struct Layer {
   float *g_attn = nullptr, *g_ff = nullptr;  // UNetT RMSNorm gains
   Lin qkv_g, ff1_g;  // UNetT RMSNorm fold: qkv / ff1 with the norm's gain folded in, W diag(g) (same bias)
   float *q_norm_w = nullptr, *k_norm_w = nullptr;  // qk_norm = "rms_norm": the [64] gains of q_norm / k_norm (fp32)
+  // MMDiT text stream (modules.py:411-427, 807-812): to_{q,k,v}_c, to_out_c, ff_c and the c_q_norm / c_k_norm gains;
+  // the last block (context_pre_only) has qkv_c only
+  Lin qkv_c, out_c, ff1_c, ff2_c;
+  float *cq_norm_w = nullptr, *ck_norm_w = nullptr;
 };
+// AdaLN backbones (a per-step modulation table, L = N rows per sequence): DiT and MMDiT
+static bool adaln_bb(const f5h_arch& a) { return a.backbone != F5H_UNETT; }
+// MMDiT AdaLN table row: per block the audio stream's 6d (attn_norm_x) then the text stream's 6d (attn_norm_c; 2d
+// (scale, shift) in the last block, AdaLayerNorm_Final), then norm_out's 2d
+static size_t mm_ada_x(const f5h_arch& a, int l) { return (size_t)l * 12 * a.dim; }
+static size_t mm_ada_c(const f5h_arch& a, int l) { return mm_ada_x(a, l) + (size_t)6 * a.dim; }
+static size_t mm_ada_fin(const f5h_arch& a) { return mm_ada_c(a, a.depth - 1) + (size_t)2 * a.dim; }
+constexpr int kMMTextPos = 1024;  // TextEmbedding.precompute_max_pos (mmdit.py:39)
 
 struct GraphKey {
   const void* ws;
   int kind;  // 0: one NFE step, 1: the call prologue (inputs staged into the workspace)
   int B, N, nt, nfe, use_cfg, batch_mask, probe, split, pad_skip, chain, lnfold, store;
   int method;  // f5h_ode_method (nfe counts evaluations = table rows: steps x stages)
+  // MMDiT single-branch forward (kind 2): the captured step reads the text stream's start from the conditional or the
+  // dropped-text embedding, so drop_text is part of the key (DiT / UNetT: the drop flags act in the prologue only)
+  int drop_text;
   uint64_t kernel_epoch;  // bumped whenever a forced GEMM config changes
   uint32_t cfg_bits;
   bool operator==(const GraphKey& o) const {
     return ws == o.ws && kind == o.kind && B == o.B && N == o.N && nt == o.nt && nfe == o.nfe && kernel_epoch == o.kernel_epoch &&
            use_cfg == o.use_cfg && batch_mask == o.batch_mask && probe == o.probe && cfg_bits == o.cfg_bits &&
            split == o.split && pad_skip == o.pad_skip && chain == o.chain && lnfold == o.lnfold && store == o.store &&
-           method == o.method;
+           method == o.method && drop_text == o.drop_text;
   }
 };
 
@@ -366,8 +381,108 @@ static int pack_conv_weight(const void* src, int src_dt, int d, void* dst, int d
   return 0;
 }
 
+// precompute_freqs_cis(dim, rows) (modules.py:207-218): [rows][cos(p f_i) for i < dim/2 | sin(p f_i)]
+static std::vector<float> freqs_cis(int dim, int rows) {
+  std::vector<float> fc((size_t)rows * dim);
+  const int half = dim / 2;
+  for (int p = 0; p < rows; ++p)
+    for (int i = 0; i < half; ++i) {
+      float f = 1.0f / std::pow(10000.0f, (float)(2 * i) / (float)dim);
+      float ang = (float)p * f;
+      fc[(size_t)p * dim + i] = std::cos(ang);
+      fc[(size_t)p * dim + half + i] = std::sin(ang);
+    }
+  return fc;
+}
+
+// [q | k | v] panel of three [inner][d] linears with their biases
+static int pack_qkv(f5h_engine* e, const WMap& W, const std::string& pa, const char* sfx, int inner, int d, Lin* L,
+                    std::string* err) {
+  const WView *w[3], *b[3];
+  const char* n[3] = {"to_q", "to_k", "to_v"};
+  for (int j = 0; j < 3; ++j) {
+    w[j] = W.get(pa + n[j] + sfx + ".weight", (int64_t)inner * d, err);
+    if (!w[j]) return fail(F5H_ENOWEIGHT, *err);
+    b[j] = W.get(pa + n[j] + sfx + ".bias", inner, err);
+    if (!b[j]) return fail(F5H_ENOWEIGHT, *err);
+  }
+  return make_lin(e, {Block{w[0], inner, d, 0, d, 0}, Block{w[1], inner, d, 0, d, 0}, Block{w[2], inner, d, 0, d, 0}},
+                  d, {b[0], b[1], b[2]}, L);
+}
+
+// MMDiT (mmdit.py:87-133) under the reference's names
+static int pack_mmdit(f5h_engine* e, const WMap& W) {
+  const f5h_arch& a = e->a;
+  const int d = a.dim, inner = a.heads * a.dim_head, F = a.ff_dim, mel = a.mel_dim;
+  const int V = a.text_num_embeds + 1;
+  std::string err;
+  RC(lin_simple(e, W, "time_embed.time_mlp.0.weight", "time_embed.time_mlp.0.bias", d, 256, &e->t1, &err));
+  RC(lin_simple(e, W, "time_embed.time_mlp.2.weight", "time_embed.time_mlp.2.bias", d, d, &e->t2, &err));
+  RC(vec_upload(e, W, "text_embed.text_embed.weight", (int64_t)V * d, &e->text_table, &err));
+  RC(upload(e, freqs_cis(d, kMMTextPos), &e->freqs));
+  // audio_embed.linear over cat(x, cond) (mmdit.py:78-79): the x columns per evaluation, the cond columns and the bias
+  // hoisted (the DiT input projection without its text columns)
+  {
+    const WView* w = W.get("audio_embed.linear.weight", (int64_t)d * 2 * mel, &err);
+    const WView* b = w ? W.get("audio_embed.linear.bias", d, &err) : nullptr;
+    if (!w || !b) return fail(F5H_ENOWEIGHT, err);
+    RC(make_lin(e, {Block{w, d, 2 * mel, 0, mel, 0}}, 128, {}, &e->in_x));
+    RC(make_lin(e, {Block{w, d, 2 * mel, mel, mel, 0}}, 128, {b}, &e->in_ct));
+  }
+  for (int j = 0; j < 2; ++j) {
+    const std::string p = "audio_embed.conv_pos_embed.conv1d." + std::to_string(j * 2) + ".";
+    const WView* w = W.get(p + "weight", (int64_t)d * (d / 16) * 31, &err);
+    if (!w) return fail(F5H_ENOWEIGHT, err);
+    RC(dalloc(e, kConvPackElems * e->esz, &e->conv_w[j]));
+    RC(pack_conv_weight(w->p, w->dt, d, e->conv_w[j], op_dt(e), e->mstream));
+    RC(vec_upload(e, W, p + "bias", d, &e->conv_b[j], &err));
+  }
+  e->layers.resize(a.depth);
+  std::vector<Block> ada_blocks;
+  std::vector<const WView*> ada_bias;
+  auto ada_push = [&](const std::string& n, int rows) -> int {
+    const WView* aw = W.get(n + ".linear.weight", (int64_t)rows * d, &err);
+    const WView* ab = aw ? W.get(n + ".linear.bias", rows, &err) : nullptr;
+    if (!aw || !ab) return fail(F5H_ENOWEIGHT, err);
+    ada_blocks.push_back(Block{aw, rows, d, 0, d, 0});
+    ada_bias.push_back(ab);
+    return 0;
+  };
+  for (int l = 0; l < a.depth; ++l) {
+    Layer& L = e->layers[l];
+    const bool last = l == a.depth - 1;  // context_pre_only (mmdit.py:124)
+    const std::string p = "transformer_blocks." + std::to_string(l) + ".";
+    const std::string pa = p + "attn.";
+    RC(ada_push(p + "attn_norm_x", 6 * d));
+    RC(ada_push(p + "attn_norm_c", last ? 2 * d : 6 * d));
+    RC(pack_qkv(e, W, pa, "", inner, d, &L.qkv, &err));
+    RC(pack_qkv(e, W, pa, "_c", inner, d, &L.qkv_c, &err));
+    if (a.qk_norm) {
+      const char* nn[4] = {"q_norm.weight", "k_norm.weight", "c_q_norm.weight", "c_k_norm.weight"};
+      float** dst[4] = {&L.q_norm_w, &L.k_norm_w, &L.cq_norm_w, &L.ck_norm_w};
+      for (int j = 0; j < 4; ++j) {
+        if (!W.get(pa + nn[j], a.dim_head, &err)) return fail(F5H_ENOWEIGHT, "qk_norm: " + err);
+        RC(vec_upload(e, W, pa + nn[j], a.dim_head, dst[j], &err));
+      }
+    }
+    RC(lin_simple(e, W, pa + "to_out.0.weight", pa + "to_out.0.bias", d, inner, &L.out, &err));
+    RC(lin_simple(e, W, p + "ff_x.ff.0.0.weight", p + "ff_x.ff.0.0.bias", F, d, &L.ff1, &err));
+    RC(lin_simple(e, W, p + "ff_x.ff.2.weight", p + "ff_x.ff.2.bias", d, F, &L.ff2, &err));
+    if (!last) {
+      RC(lin_simple(e, W, pa + "to_out_c.weight", pa + "to_out_c.bias", d, inner, &L.out_c, &err));
+      RC(lin_simple(e, W, p + "ff_c.ff.0.0.weight", p + "ff_c.ff.0.0.bias", F, d, &L.ff1_c, &err));
+      RC(lin_simple(e, W, p + "ff_c.ff.2.weight", p + "ff_c.ff.2.bias", d, F, &L.ff2_c, &err));
+    }
+  }
+  RC(ada_push("norm_out", 2 * d));
+  RC(make_lin(e, ada_blocks, d, ada_bias, &e->ada));
+  RC(lin_simple(e, W, "proj_out.weight", "proj_out.bias", mel, d, &e->proj_out, &err));
+  return 0;
+}
+
 static int pack_all(f5h_engine* e, const WMap& W) {
   const f5h_arch& a = e->a;
+  if (a.backbone == F5H_MMDIT) return pack_mmdit(e, W);
   const int d = a.dim, inner = a.heads * a.dim_head, F = a.ff_dim, td = a.text_dim, mel = a.mel_dim;
   const int V = a.text_num_embeds + 1;
   std::string err;
@@ -537,6 +652,9 @@ struct Bufs {
   // long skip connection (residual dtype); the text embedding after average upsampling [2][B][N][td]
   void* hkeep;
   float* te_up;
+  // MMDiT text stream (null otherwise), see layout
+  void *c0, *ch, *caop, *co, *cf;
+  uint8_t* ckeep;
   // UNetT residual stream (operand dtype): xs[0..depth/2] -- layer l < depth/2 reads xs[l] (its
   // skip connection, kept) and writes xs[l+1]; later layers ping-pong between pp[0] and pp[1]
   std::vector<void*> xs;
@@ -550,19 +668,22 @@ struct Bufs {
 };
 
 // nfe: table rows. method / steps: the multi-stage solvers' extra buffers (none for Euler, whose layout is unchanged)
+// nt: text tokens (MMDiT only: its text stream's buffers; the other backbones' layouts do not depend on it)
 static void layout(const f5h_engine* e, WS& ws, Bufs& b, int B, int N, int nfe, int use_cfg, int method = 0,
-                   int steps = 0) {
+                   int steps = 0, int nt = 0) {
   const f5h_arch& a = e->a;
   const int d = a.dim, td = a.text_dim, S = use_cfg ? 2 * B : B;
-  const int L = a.backbone == F5H_DIT ? N : N + 1;
+  const bool mm = a.backbone == F5H_MMDIT;
+  const int L = adaln_bb(a) ? N : N + 1;
   const size_t rows = (size_t)S * L, es = e->esz;
+  const size_t jrows = mm ? (size_t)S * (N + nt) : rows;  // rows of the q / k / v buffers (MMDiT: the joint sequence)
   const int inner = a.heads * 64;
   b.tsin = ws.take<float>((size_t)nfe * 256);
   b.th = ws.take<float>((size_t)nfe * d);
   b.temb = ws.take<float>((size_t)nfe * d);
   b.tin_op = ws.take<char>((size_t)nfe * std::max(256, d) * es);
-  b.ada = a.backbone == F5H_DIT ? ws.take<float>((size_t)nfe * e->ada_row) : nullptr;
-  b.te = ws.take<float>((size_t)2 * B * N * td);
+  b.ada = adaln_bb(a) ? ws.take<float>((size_t)nfe * e->ada_row) : nullptr;
+  b.te = ws.take<float>((size_t)2 * B * (mm ? nt : N) * td);  // (MMDiT: [2][B][nt][d], not padded to the audio length)
   b.keepfill = ws.take<uint8_t>((size_t)2 * B * N);
   if (a.conv_layers > 0) {
     b.dwln = ws.take<char>((size_t)2 * B * N * td * es);
@@ -578,20 +699,20 @@ static void layout(const f5h_engine* e, WS& ws, Bufs& b, int B, int N, int nfe, 
   b.ypad = ws.take<char>((size_t)B * N * 128 * es);
   b.h0 = ws.take<float>((size_t)S * N * d);
   b.c1 = ws.take<char>((size_t)S * N * d * es);
-  b.h = a.backbone == F5H_DIT ? ws.take<float>(rows * d) : nullptr;  // DiT residual stream
+  b.h = adaln_bb(a) ? ws.take<float>(rows * d) : nullptr;  // DiT / MMDiT (audio) residual stream
   b.aop = ws.take<char>(rows * d * es);
-  b.q = ws.take<char>(rows * inner * es);
-  b.k = ws.take<char>(rows * inner * es);
-  b.v = ws.take<char>(rows * inner * es);
+  b.q = ws.take<char>(jrows * inner * es);
+  b.k = ws.take<char>(jrows * inner * es);
+  b.v = ws.take<char>(jrows * inner * es);
   b.o = ws.take<char>(rows * inner * es);
   b.f = ws.take<char>(rows * a.ff_dim * es);
   b.p = ws.take<float>(rows * e->proj_out.Npad);  // proj_out rows padded to the GEMM tile width
-  b.rope = ws.take<float2>((size_t)L * 32);
+  b.rope = ws.take<float2>((size_t)(mm ? std::max(N, nt) : L) * 32);  // (MMDiT: both streams count from 0)
   b.rowkeep = ws.take<uint8_t>(rows);
   b.kvlen = ws.take<int32_t>(S);
   b.chain_g4 = ((int)((rows + kChainRows - 1) / kChainRows) + 3) / 4 * 4;
   b.chain = a.backbone == F5H_DIT ? ws.take<unsigned>((size_t)a.depth * 5 * b.chain_g4) : nullptr;
-  b.ada_cur = a.backbone == F5H_DIT ? ws.take<float>((size_t)e->ada_row) : nullptr;
+  b.ada_cur = adaln_bb(a) ? ws.take<float>((size_t)e->ada_row) : nullptr;
   // LayerNorm fold: per row and 64-column strip of the residual stream, (mean, M2) (float2)
   b.lnp = (e->lnf_ok || e->rmsf_ok) ? ws.take<float>(rows * (size_t)(d / 64) * 2) : nullptr;
   b.temb_cur = ws.take<float>((size_t)d);
@@ -601,7 +722,7 @@ static void layout(const f5h_engine* e, WS& ws, Bufs& b, int B, int N, int nfe, 
   b.trajp = ws.take<float*>(8);
   b.in_cond = ws.take<float>((size_t)B * N * a.mel_dim);
   b.in_mask = ws.take<uint8_t>((size_t)B * N);
-  b.in_text = ws.take<int64_t>((size_t)B * N);
+  b.in_text = ws.take<int64_t>((size_t)B * (mm ? std::max(N, nt) : N));
   b.in_dur = ws.take<int32_t>((size_t)B);
   b.xs.clear();
   b.pp[0] = b.pp[1] = nullptr;
@@ -616,6 +737,15 @@ static void layout(const f5h_engine* e, WS& ws, Bufs& b, int B, int N, int nfe, 
   // the options' buffers come last, so every other buffer sits where it does without them
   b.hkeep = a.long_skip_connection ? ws.take<char>(rows * d * es) : nullptr;
   b.te_up = a.text_average_upsampling ? ws.take<float>((size_t)2 * B * N * td) : nullptr;
+  // MMDiT text stream [S, nt, .]: the call-constant embedding c0 in the residual dtype (both branches; the fp32 mode
+  // reads b.te itself), the stream, its norm / attention / FFN operands and the c_mask bytes
+  const size_t crows = (size_t)S * nt, hsz = e->bf ? es : sizeof(float);
+  b.c0 = (mm && e->bf) ? ws.take<char>((size_t)2 * B * nt * d * es) : nullptr;
+  b.ch = mm ? ws.take<char>(crows * d * hsz) : nullptr;
+  b.caop = mm ? ws.take<char>(crows * d * es) : nullptr;
+  b.co = mm ? ws.take<char>(crows * inner * es) : nullptr;
+  b.cf = mm ? ws.take<char>(crows * a.ff_dim * es) : nullptr;
+  b.ckeep = mm ? ws.take<uint8_t>(crows) : nullptr;
 }
 
 // ---------------------------------------------------------------- probe
@@ -710,8 +840,10 @@ static int prologue(Ctx& c, const float* t_host, int nt_vals, const float* cond,
   const int d = a.dim, td = a.text_dim, bf = e->bf;
   Bufs& b = c.b;
   hipStream_t st = c.st;
-  KCK(rope_table(c.L, b.rope, st));
-  const int off = a.backbone == F5H_DIT ? 0 : 1;
+  const bool mm = a.backbone == F5H_MMDIT;
+  KCK(rope_table(mm ? std::max(c.N, c.nt) : c.L, b.rope, st));
+  if (mm) KCK(build_textkeep(text, c.B, c.S, c.nt, b.ckeep, st));  // c_mask (mmdit.py:232), both branches
+  const int off = adaln_bb(a) ? 0 : 1;
   if (c.batch_mask) {
     KCK(build_rowkeep(duration, c.B, c.S, c.L, off, b.rowkeep, st));
     KCK(build_kvlen(duration, c.B, c.S, off, b.kvlen, st));
@@ -728,7 +860,7 @@ static int prologue(Ctx& c, const float* t_host, int nt_vals, const float* cond,
     KCK(f32_to_op(bf, b.th, (int64_t)nt_vals * d, b.tin_op, st));
     g = gargs(b.tin_op, d, e->t2, nt_vals, b.temb, d);
     KCK(gemm(bf, EPI_STORE, g, st));
-    if (a.backbone == F5H_DIT) {
+    if (adaln_bb(a)) {
       KCK(silu_to_op(bf, b.temb, b.tin_op, (int64_t)nt_vals * d, st));
       g = gargs(b.tin_op, d, e->ada, nt_vals, b.ada, e->ada_row);
       KCK(gemm(bf, EPI_STORE, g, st));
@@ -749,7 +881,24 @@ static int prologue(Ctx& c, const float* t_host, int nt_vals, const float* cond,
   }
   // ---- text embedding, both branches (cached once per call in the reference, dit.py:294-310);
   // text_cached: the plugin's kept embedding is already in the workspace (f5h_forward text_cache 2)
-  if (!text_cached) {
+  if (!text_cached && mm) {
+    // mmdit.py:32-63: Embedding(text + 1) [nt, dim] + freqs_cis[min(j, 1023)], filler rows (taken before drop_text)
+    // zeroed; no ConvNeXt blocks, not padded to the audio length. Both branches, then once into the residual dtype
+    TextEmbArgs t{};
+    t.text = text;
+    t.B = c.B;
+    t.nt = c.nt;
+    t.N = c.nt;
+    t.td = d;
+    t.table = e->text_table;
+    t.freqs = e->freqs;
+    t.freq_rows = kMMTextPos;
+    t.mask_padding = a.text_mask_padding;
+    t.out_c = b.te;
+    t.out_u = b.te + (size_t)c.B * c.nt * d;
+    KCK(text_embed(t, st));
+    if (bf) KCK(f32_to_op(bf, b.te, (int64_t)2 * c.B * c.nt * d, b.c0, st));
+  } else if (!text_cached) {
     TextEmbArgs t{};
     t.text = text;
     t.B = c.B;
@@ -793,7 +942,8 @@ static int prologue(Ctx& c, const float* t_host, int nt_vals, const float* cond,
   }
   // ---- hoisted input projection: P = [step_cond | text] . W_ct^T + b
   const float* te = a.text_average_upsampling ? b.te_up : b.te;
-  KCK(build_ct(bf, cond, cond_mask, te, te + (size_t)c.B * c.N * td, c.B, c.N, td, c.S, c.drop_audio,
+  // (MMDiT: no text columns, the audio embedding sees cat(x, cond) only)
+  KCK(build_ct(bf, cond, cond_mask, te, te + (size_t)c.B * c.N * td, c.B, c.N, mm ? 0 : td, c.S, c.drop_audio,
                c.drop_text, b.act, st));
   GemmArgs g = gargs(b.act, 128 + e->tdp, e->in_ct, c.S * c.N, b.P, d);
   KCK(gemm(bf, EPI_STORE, g, st));
@@ -806,7 +956,7 @@ constexpr int kArrive = 16;
 // Copy the step's table row (k = *kstep) to the fixed per-step buffer the layers read.
 static int step_prep(Ctx& c) {
   f5h_engine* e = c.e;
-  if (e->a.backbone == F5H_DIT)
+  if (adaln_bb(e->a))
     KCK(step_begin(c.b.kstep, c.b.ada, e->ada_row, e->ada_row, c.b.ada_cur, c.st));
   else
     KCK(step_begin(c.b.kstep, c.b.temb, e->a.dim, e->a.dim, c.b.temb_cur, c.st));
@@ -1144,11 +1294,168 @@ static int backbone_part(Ctx& c, int s0, int ns, hipStream_t st) {
   return 0;
 }
 
+// The MMDiT backbone (mmdit.py:214-262, modules.py:563-705, 763-846) for all S sequences of the current step; result in
+// b.p. Two residual streams, audio h [S,N,d] and text ch [S,nt,d] (it restarts from the call-constant embedding c0 at
+// every evaluation: block 0's text-side residual GEMM reads c0 and writes ch, so c0 is never copied). Per block: both
+// streams' LN-modulate, two QKV launches into the joint q / k / v [S,H,N+nt,64] (audio rows [0,N), text rows [N,N+nt)
+// of every panel, each stream rotated from position 0, GemmArgs::qkv_dst_len), one attention over N + nt rows with the
+// output split back (AttnArgs::o_split), then per stream the out-projection, LN-modulate, FFN1 and FFN2 with the
+// kernels the DiT block uses. The last block (context_pre_only) only pre-normalises the text stream, with
+// AdaLayerNorm_Final's (scale, shift) order. No key is masked (pad audio and pad text keys are attended, as in the
+// reference without attn_mask_enabled); audio rows are zeroed where ~mask on batch calls, text rows where text == -1
+// always (modules.py:700-703). No phase chain, LayerNorm fold or pad-row skip: the joint layout's live rows are not
+// a prefix, and the fold's producers / consumers would need the text stream's statistics buffers.
+static int backbone_mmdit(Ctx& c, hipStream_t st) {
+  f5h_engine* e = c.e;
+  const f5h_arch& a = e->a;
+  const int d = a.dim, bf = e->bf, H = a.heads, inner = H * 64, F = a.ff_dim;
+  const size_t es = e->esz;
+  Bufs& b = c.b;
+  const int BN = c.B * c.N, rows = c.S * c.N, crows = c.S * c.nt, Lj = c.N + c.nt;
+  const bool r16 = bf != 0;  // residual streams in the operand dtype (16-bit modes), fp32 in the fp32 mode
+  const int epi_resid = r16 ? EPI_RESID16 : EPI_RESID;
+  const uint8_t* keep = c.batch_mask ? b.rowkeep : nullptr;
+  // ---- audio embedding (mmdit.py:75-81): h0 = y.Wx^T + P, then conv_pos_embed(h0) + h0 (no mask there)
+  {
+    GemmArgs g = gargs(b.ypad, 128, e->in_x, BN, b.h0, d);
+    g.bias = nullptr;
+    g.add = b.P;
+    g.ld_add = d;
+    g.dual_rows = c.S == 2 * c.B ? BN : 0;
+    KCK(gemm(bf, EPI_INPROJ, g, st));
+    ConvArgs cv{};
+    cv.S = c.S;
+    cv.L = c.N;
+    cv.d = d;
+    cv.x = b.h0;
+    cv.x_f32 = 1;
+    cv.w = e->conv_w[0];
+    cv.bias = e->conv_b[0];
+    cv.mode = 0;
+    cv.y = b.c1;
+    {
+      ProbeScope ps(e, KC_CONV, st, &c.site);
+      KCK(conv_pos(bf, cv, st));
+    }
+    cv.x = b.c1;
+    cv.x_f32 = bf ? 0 : 1;
+    cv.w = e->conv_w[1];
+    cv.bias = e->conv_b[1];
+    cv.mode = r16 ? 2 : 1;
+    cv.y = b.h;
+    cv.y_seq_stride = c.N;
+    cv.y_row_off = 0;
+    cv.resid = b.h0;
+    KCK(conv_pos(bf, cv, st));
+  }
+  // the text stream's start: the conditional rows then the unconditional ones (packed), or the branch asked for
+  const char* te0 = r16 ? (const char*)b.c0 : (const char*)b.te;
+  const size_t hsz = r16 ? es : sizeof(float);
+  const void* c0 = te0 + ((c.S == c.B && c.drop_text) ? (size_t)c.B * c.nt * d * hsz : 0);
+  const float* ada_k = b.ada_cur;
+  auto count_store = [&](int wt) { (wt ? e->n_store_wt : e->n_store_plain).fetch_add(1, std::memory_order_relaxed); };
+  auto gemm_policy = [&](GemmArgs& g, int epi, int kclass) {
+    g.store_wt = gemm_store_wt(bf, epi, g, store_want(c.store, kclass));
+    count_store(g.store_wt);
+  };
+  auto qkv = [&](const void* A, const Lin& W, int M, int seq, size_t row0, const float* qn, const float* kn) -> int {
+    GemmArgs g = gargs(A, d, W, M, nullptr, 0);
+    g.rope = b.rope;
+    g.seq_len = seq;
+    g.qkv_dst_len = Lj;
+    g.heads = H;
+    g.rope_heads = H;
+    g.q = (char*)b.q + row0 * 64 * es;
+    g.k = (char*)b.k + row0 * 64 * es;
+    g.v = (char*)b.v + row0 * 64 * es;
+    g.q_scale = 0.125f * 1.4426950408889634f;  // softmax scale 1/sqrt(64) in log2 units, folded into q
+    g.q_norm_w = qn;
+    g.k_norm_w = kn;
+    g.qk_norm_eps = 1e-6f;
+    gemm_policy(g, EPI_QKV, KC_QKV);
+    ProbeScope ps(e, KC_QKV, st, &c.site, &g.probe);
+    KCK(gemm(bf, EPI_QKV, g, st));
+    return 0;
+  };
+  // out-projection or FFN2 of one stream: C += gate (acc + bias) on kept rows, the residual read from `resid` when set
+  auto resid_gemm = [&](const void* A, int K, const Lin& W, int M, void* C, const void* resid, const float* gate,
+                        const uint8_t* rk, int kclass) -> int {
+    GemmArgs g = gargs(A, K, W, M, C, d);
+    g.resid = resid;
+    g.gate = gate;
+    g.rowkeep = rk;
+    gemm_policy(g, epi_resid, kclass);
+    ProbeScope ps(e, kclass, st, &c.site, &g.probe);
+    KCK(gemm(bf, epi_resid, g, st));
+    return 0;
+  };
+  auto ffn1 = [&](const void* A, const Lin& W, int M, void* out) -> int {
+    GemmArgs g = gargs(A, d, W, M, out, F);
+    gemm_policy(g, EPI_GELU_TANH, KC_FFN1);
+    ProbeScope ps(e, KC_FFN1, st, &c.site, &g.probe);
+    KCK(gemm(bf, EPI_GELU_TANH, g, st));
+    return 0;
+  };
+  for (int l = 0; l < a.depth; ++l) {
+    Layer& Ly = e->layers[l];
+    const bool last = l == a.depth - 1;
+    const float* ax = ada_k + mm_ada_x(a, l);  // (shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp)
+    const float* ac = ada_k + mm_ada_c(a, l);  // the same, or (scale, shift) in the last block
+    const void* c_in = l == 0 ? c0 : b.ch;
+    KCK(ln_modulate(bf, b.h, r16, rows, d, ax, ax + d, b.aop, st));
+    KCK(ln_modulate(bf, c_in, r16, crows, d, last ? ac + d : ac, last ? ac : ac + d, b.caop, st));
+    RC(qkv(b.aop, Ly.qkv, rows, c.N, 0, Ly.q_norm_w, Ly.k_norm_w));
+    RC(qkv(b.caop, Ly.qkv_c, crows, c.nt, (size_t)c.N, Ly.cq_norm_w, Ly.ck_norm_w));
+    {
+      AttnArgs at{};
+      at.q = b.q;
+      at.k = b.k;
+      at.v = b.v;
+      at.o = b.o;
+      at.o2 = b.co;
+      at.o_split = c.N;
+      at.S = c.S;
+      at.H = H;
+      at.L = Lj;
+      at.scale = 0.125f;
+      at.prescaled = 1;
+      at.store_wt = attention_store_wt(bf, at, store_want(c.store, KC_ATTN));
+      count_store(at.store_wt);
+      ProbeScope ps(e, KC_ATTN, st, &c.site, &at.probe);
+      KCK(attention(bf, at, st));
+    }
+    RC(resid_gemm(b.o, inner, Ly.out, rows, b.h, nullptr, ax + 2 * d, keep, KC_OUT));
+    if (!last) RC(resid_gemm(b.co, inner, Ly.out_c, crows, b.ch, l == 0 ? c0 : nullptr, ac + 2 * d, b.ckeep, KC_OUT));
+    {
+      ProbeScope ps(e, KC_NORM, st, &c.site);
+      KCK(ln_modulate(bf, b.h, r16, rows, d, ax + 3 * d, ax + 4 * d, b.aop, st));
+    }
+    RC(ffn1(b.aop, Ly.ff1, rows, b.f));
+    RC(resid_gemm(b.f, F, Ly.ff2, rows, b.h, nullptr, ax + 5 * d, nullptr, KC_FFN2));
+    if (!last) {
+      {
+        ProbeScope ps(e, KC_NORM, st, &c.site);
+        KCK(ln_modulate(bf, b.ch, r16, crows, d, ac + 3 * d, ac + 4 * d, b.caop, st));
+      }
+      RC(ffn1(b.caop, Ly.ff1_c, crows, b.cf));
+      RC(resid_gemm(b.cf, F, Ly.ff2_c, crows, b.ch, nullptr, ac + 5 * d, nullptr, KC_FFN2));
+    }
+  }
+  const float* fin = ada_k + mm_ada_fin(a);  // AdaLayerNorm_Final: (scale, shift)
+  KCK(ln_modulate(bf, b.h, r16, rows, d, fin + d, fin, b.aop, st));
+  const int pld = e->proj_out.Npad;
+  GemmArgs g = gargs(b.aop, d, e->proj_out, rows, b.p, pld);
+  g.N = pld;
+  KCK(gemm(bf, EPI_STORE, g, st));
+  return 0;
+}
+
 // One packed cond/uncond backbone forward for the current step; result in b.p [S, L, mel]. With a
 // second stream (c.st2, graph capture only) the conditional and unconditional branches run as two
 // independent launch chains (fork/join by events), so one chain's kernel heads and tails overlap
 // the other's bodies instead of leaving CUs idle at every kernel boundary.
 static int backbone_step(Ctx& c) {
+  if (c.e->a.backbone == F5H_MMDIT) return backbone_mmdit(c, c.st);  // always one chain (f5h_set_cfg_streams: no effect)
   if (!c.st2 || !c.use_cfg) return backbone_part(c, 0, c.S, c.st);
   f5h_engine* e = c.e;
   KCK(hipEventRecord(e->ev_fork, c.st));
@@ -1292,13 +1599,23 @@ static int chain_fault_note(f5h_engine* e, hipStream_t st) {
 
 static int check_arch(const f5h_arch* a) {
   if (!a) return fail(F5H_EINVAL, "null arch");
-  if (a->backbone != F5H_DIT && a->backbone != F5H_UNETT) return fail(F5H_EINVAL, "backbone must be DiT or UNetT");
+  if (a->backbone != F5H_DIT && a->backbone != F5H_UNETT && a->backbone != F5H_MMDIT)
+    return fail(F5H_EINVAL, "backbone must be DiT, UNetT or MMDiT");
+  if (a->backbone == F5H_MMDIT) {  // mmdit.py:87-133: one width for both streams, no ConvNeXt text blocks, RoPE on all heads
+    if (a->text_dim != a->dim) return fail(F5H_EINVAL, "MMDiT: text_dim must equal dim");
+    if (a->conv_layers != 0) return fail(F5H_EINVAL, "MMDiT: conv_layers must be 0");
+    if (a->pe_attn_head != 0) return fail(F5H_EINVAL, "MMDiT: pe_attn_head must be 0");
+    if (a->long_skip_connection != 0) return fail(F5H_EINVAL, "MMDiT: long_skip_connection must be 0");
+    if (a->text_average_upsampling != 0) return fail(F5H_EINVAL, "MMDiT: text_average_upsampling must be 0");
+    if (a->depth < 1) return fail(F5H_EINVAL, "MMDiT: depth must be >= 1");
+  }
   if (a->dim_head != 64) return fail(F5H_EINVAL, "dim_head must be 64");
   if (a->dim % 128 || a->dim <= 0 || a->dim > 1024) return fail(F5H_EINVAL, "dim must be a multiple of 128, <= 1024");
   if (a->heads * 64 != a->dim) return fail(F5H_EINVAL, "heads*dim_head must equal dim");
   if (a->ff_dim % 64 || a->ff_dim <= 0) return fail(F5H_EINVAL, "ff_dim must be a positive multiple of 64");
   if (a->mel_dim != 100) return fail(F5H_EINVAL, "mel_dim must be 100");
-  if (a->text_dim <= 0 || a->text_dim % 4 || a->text_dim > 512) return fail(F5H_EINVAL, "text_dim must be <= 512, % 4");
+  if (a->backbone != F5H_MMDIT && (a->text_dim <= 0 || a->text_dim % 4 || a->text_dim > 512))
+    return fail(F5H_EINVAL, "text_dim must be <= 512, % 4");
   if (a->depth <= 0 || (a->backbone == F5H_UNETT && a->depth % 2)) return fail(F5H_EINVAL, "bad depth");
   if (a->backbone == F5H_UNETT && a->conv_layers != 0) return fail(F5H_EINVAL, "UNetT with conv_layers unsupported");
   if (a->compute != F5H_FP32 && a->compute != F5H_BF16 && a->compute != F5H_FP16)
@@ -1344,7 +1661,8 @@ int f5h_engine_create_views(const f5h_arch* arch, const f5h_tensor_view* weights
   e->dev = device;
   e->bf = arch->compute;
   e->esz = e->bf ? 2 : 4;
-  e->tdp = (arch->text_dim + 63) / 64 * 64;
+  // text columns of the hoisted input projection (none for MMDiT: its text is a stream of its own)
+  e->tdp = arch->backbone == F5H_MMDIT ? 0 : (arch->text_dim + 63) / 64 * 64;
   if (const char* gv = getenv("F5H_GRAPH")) e->graph_mode = atoi(gv) ? 1 : 0;
   if (const char* sv = getenv("F5H_SPLIT_CFG")) e->split_cfg = std::min(2, std::max(0, atoi(sv)));
   if (const char* pv = getenv("F5H_NO_PAD_SKIP")) e->pad_skip = (*pv == '1') ? 0 : 1;
@@ -1405,6 +1723,7 @@ int f5h_engine_create_views(const f5h_arch* arch, const f5h_tensor_view* weights
       if (upload(e, wp, &e->lnf_w)) e->lnf_ok = false;
     }
   }
+  if (!rc && arch->backbone == F5H_MMDIT) e->ada_row = e->ada.Npad;  // no fold: the modulation rows only
   // RMSNorm fold support (UNetT, 16-bit): every layer's QKV and FFN1 weights with their norm's gain folded in
   if (!rc && arch->backbone == F5H_UNETT && e->bf != 0 && arch->dim % 64 == 0 && arch->dim <= 1024) {
     e->rmsf_ok = true;
@@ -1506,11 +1825,12 @@ void f5h_engine_destroy(f5h_engine* e) {
 
 size_t f5h_workspace_size_ode(const f5h_engine* e, int32_t B, int32_t N, int32_t nt, int32_t steps, int32_t use_cfg,
                              int32_t method) {
-  (void)nt;
   if (!e || B <= 0 || N <= 0 || steps <= 0 || method < 0 || method >= kOdeMethods) return 0;
+  if (e->a.backbone == F5H_MMDIT && nt < 0) return 0;
   WS ws;
   Bufs b;
-  layout(e, ws, b, B, N, steps * ode_tableau(method).stages + 1, use_cfg, method, steps);
+  layout(e, ws, b, B, N, steps * ode_tableau(method).stages + 1, use_cfg, method, steps,
+         e->a.backbone == F5H_MMDIT ? nt : 0);
   return ws.off;
 }
 size_t f5h_workspace_size(const f5h_engine* e, int32_t B, int32_t N, int32_t nt, int32_t nfe, int32_t use_cfg) {
@@ -1521,12 +1841,22 @@ size_t f5h_workspace_size(const f5h_engine* e, int32_t B, int32_t N, int32_t nt,
 static int check_ws(f5h_engine* e, int B, int N, int nfe, int use_cfg, void* w, size_t bytes, Ctx& c, int method = 0,
                     int steps = 0) {
   WS ws;
-  layout(e, ws, c.b, B, N, nfe + 1, use_cfg, method, steps);
+  layout(e, ws, c.b, B, N, nfe + 1, use_cfg, method, steps, c.nt);
   if (bytes < ws.off)
     return fail(F5H_ENOMEM, "workspace too small: need " + std::to_string(ws.off) + " have " + std::to_string(bytes));
   ws.off = 0;
   ws.base = reinterpret_cast<char*>(w);
-  layout(e, ws, c.b, B, N, nfe + 1, use_cfg, method, steps);
+  layout(e, ws, c.b, B, N, nfe + 1, use_cfg, method, steps, c.nt);
+  return 0;
+}
+// MMDiT calls (f5h_sample / f5h_forward): what the joint attention cannot serve
+static int check_mmdit_call(const f5h_engine* e, int nt, int batch_mask) {
+  if (e->a.backbone != F5H_MMDIT) return 0;
+  if (nt <= 0) return fail(F5H_EINVAL, "MMDiT needs nt >= 1 text tokens");
+  if (e->a.attn_mask_enabled && batch_mask)
+    return fail(F5H_EINVAL,
+                "MMDiT: attn_mask_enabled with a batch mask is not supported: the valid keys [0, dur) and [N, N + "
+                "text length) are not a prefix of the joint sequence, and the attention kernel masks a suffix only");
   return 0;
 }
 
@@ -1657,8 +1987,9 @@ static int sample_impl(f5h_engine* e, void* stream, const f5h_sample_args* a, in
   c.nfe = a->nfe * stages;  // evaluations: the time tables hold one row each, the step graph is replayed for each
   c.use_cfg = a->cfg_strength >= 1e-5f;
   c.S = c.use_cfg ? 2 * c.B : c.B;
-  c.L = e->a.backbone == F5H_DIT ? c.N : c.N + 1;
+  c.L = adaln_bb(e->a) ? c.N : c.N + 1;
   c.batch_mask = a->use_batch_mask ? 1 : 0;
+  RC(check_mmdit_call(e, c.nt, c.batch_mask));
   RC(check_ws(e, c.B, c.N, c.nfe, c.use_cfg, workspace, workspace_bytes, c, method, c.steps));
   RC(chain_fault_check(e, c.st));
   ChainTicket ticket;  // (declared after `used`: its event is recorded first, both after every launch of the call)
@@ -1728,7 +2059,7 @@ static int enqueue_step(Ctx& c, const f5h_sample_args* a) {
   {
     c.site = 0;
     RC(backbone_step(c));
-    const bool dit = e->a.backbone == F5H_DIT;
+    const bool dit = adaln_bb(e->a);  // an AdaLN table row per evaluation, predictions from row 0 (DiT, MMDiT)
     if (c.method != F5H_EULER) {  // one evaluation of a midpoint / rk4 step: same launches, cfg_rk for cfg_euler
       RkArgs r{};
       r.y = c.b.y;
@@ -1765,7 +2096,7 @@ static int enqueue_step(Ctx& c, const f5h_sample_args* a) {
     u.mel = e->a.mel_dim;
     u.p = c.b.p;
     u.p_seq_stride = (int64_t)c.L * e->proj_out.Npad;
-    u.p_row_off = e->a.backbone == F5H_DIT ? 0 : 1;
+    u.p_row_off = dit ? 0 : 1;
     u.p_ld = e->proj_out.Npad;
     u.use_cfg = c.use_cfg;
     u.cfg = a->cfg_strength;
@@ -1799,6 +2130,8 @@ static int run_steps(Ctx& c, const f5h_sample_args* a, const void* ws) {
   key.ws = ws;
   key.B = c.B;
   key.N = c.N;
+  // MMDiT: the step's launches and the text stream's buffers depend on nt (the other backbones' steps do not)
+  key.nt = e->a.backbone == F5H_MMDIT ? c.nt : 0;
   key.nfe = c.nfe;
   key.use_cfg = c.use_cfg;
   key.batch_mask = c.batch_mask;
@@ -1991,10 +2324,11 @@ int f5h_forward(f5h_engine* e, void* stream, const f5h_forward_args* a, void* wo
   c.S = c.use_cfg ? 2 * c.B : c.B;
   c.drop_audio = (!c.use_cfg && a->drop_audio_cond) ? 1 : 0;
   c.drop_text = (!c.use_cfg && a->drop_text) ? 1 : 0;
-  c.L = e->a.backbone == F5H_DIT ? c.N : c.N + 1;
+  c.L = adaln_bb(e->a) ? c.N : c.N + 1;
   c.batch_mask = a->use_batch_mask ? 1 : 0;
   if (e->a.backbone == F5H_DIT && a->N > 8192) return fail(F5H_EINVAL, "N exceeds the text position table (8192)");
   if (a->text_cache < 0 || a->text_cache > 2) return fail(F5H_EINVAL, "text_cache must be 0, 1 or 2");
+  RC(check_mmdit_call(e, c.nt, c.batch_mask));
   RC(check_ws(e, c.B, c.N, 1, c.use_cfg, workspace, workspace_bytes, c));
   RC(chain_fault_check(e, c.st));
   ChainTicket ticket;
@@ -2035,6 +2369,7 @@ int f5h_forward(f5h_engine* e, void* stream, const f5h_forward_args* a, void* wo
     key.chain = c.chain;
     key.lnfold = c.lnfold;
     key.store = c.store;
+    key.drop_text = e->a.backbone == F5H_MMDIT ? c.drop_text : 0;
     key.kernel_epoch = g_kernel_epoch.load();
     std::shared_ptr<GraphEntry> hold;
     RC(graph_get(c, key, false, body, hold, 1));
@@ -2043,7 +2378,7 @@ int f5h_forward(f5h_engine* e, void* stream, const f5h_forward_args* a, void* wo
   } else {
     RC(body(c));
   }
-  HIPCK(copy_pred(c.b.p, c.S, c.L, e->a.backbone == F5H_DIT ? 0 : 1, e->a.mel_dim, e->proj_out.Npad, a->pred,
+  HIPCK(copy_pred(c.b.p, c.S, c.L, adaln_bb(e->a) ? 0 : 1, e->a.mel_dim, e->proj_out.Npad, a->pred,
                   c.chain ? e->chain_fault : nullptr, c.st));
   if (c.chain) RC(chain_fault_note(e, c.st));
   return 0;
@@ -2272,8 +2607,11 @@ int f5h_debug_tile_live(const int32_t* live_len, int32_t live_seq, int32_t M, in
 
 static int op_attention_impl(void* stream, int32_t compute, int32_t S, int32_t H, int32_t N, const float* Q,
                              const float* K, const float* V, const int32_t* kv_len, const int32_t* q_len,
-                             int32_t q_prescaled, float* O, void* workspace, size_t workspace_bytes) {
+                             int32_t q_prescaled, float* O, void* workspace, size_t workspace_bytes,
+                             int32_t o_split = 0, float* O2 = nullptr) {
   if (S <= 0 || H <= 0 || N <= 0) return fail(F5H_EINVAL, "bad attention shape");
+  if (o_split < 0 || o_split >= N || (o_split > 0 && !O2))
+    return fail(F5H_EINVAL, "op_attention_split: o_split must lie in [0, N) and needs O2");
   if (compute < F5H_FP32 || compute > F5H_FP16) return fail(F5H_EINVAL, "bad compute mode");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int64_t n = (int64_t)S * H * N * 64;
@@ -2285,6 +2623,8 @@ static int op_attention_impl(void* stream, int32_t compute, int32_t S, int32_t H
   at.q_len = q_len;
   at.scale = 0.125f;
   at.prescaled = q_prescaled ? 1 : 0;
+  at.o_split = o_split;
+  const int64_t n1 = o_split ? (int64_t)S * o_split * H * 64 : n;  // elements of the first output
   if (compute) {
     const size_t need = (size_t)n * 2 * 4 + 4 * 256;
     if (workspace_bytes < need) return fail(F5H_ENOMEM, "workspace too small for op_attention");
@@ -2297,13 +2637,16 @@ static int op_attention_impl(void* stream, int32_t compute, int32_t S, int32_t H
     at.k = k;
     at.v = v;
     at.o = o;
+    at.o2 = (char*)o + n1 * 2;  // the two 16-bit outputs back to back: n elements in all
     HIPCK(attention(compute, at, st));
-    HIPCK(op_to_f32(compute, o, n, O, st));
+    HIPCK(op_to_f32(compute, o, n1, O, st));
+    if (o_split) HIPCK(op_to_f32(compute, at.o2, n - n1, O2, st));
   } else {
     at.q = Q;
     at.k = K;
     at.v = V;
     at.o = O;
+    at.o2 = O2;
     HIPCK(attention(0, at, st));
   }
   return 0;
@@ -2321,6 +2664,14 @@ int f5h_op_attention_qlen(void* stream, int32_t compute, int32_t S, int32_t H, i
                           int32_t q_prescaled, float* O, void* workspace, size_t workspace_bytes) {
   return op_attention_impl(stream, compute, S, H, N, Q, K, V, kv_len, q_len, q_prescaled, O, workspace,
                            workspace_bytes);
+}
+
+int f5h_op_attention_split(void* stream, int32_t compute, int32_t S, int32_t H, int32_t N, const float* Q,
+                           const float* K, const float* V, const int32_t* kv_len, const int32_t* q_len,
+                           int32_t q_prescaled, int32_t o_split, float* O, float* O2, void* workspace,
+                           size_t workspace_bytes) {
+  return op_attention_impl(stream, compute, S, H, N, Q, K, V, kv_len, q_len, q_prescaled, O, workspace,
+                           workspace_bytes, o_split, O2);
 }
 
 // ---- op-level entry points of the conv / norm / GEMM-epilogue kernels (tests/test_gpu_ops.py). Each validates
@@ -2494,6 +2845,10 @@ int f5h_op_gemm_epi(void* stream, const f5h_op_gemm_args* a, void* workspace, si
     if (a->heads <= 0 || N != 3 * inner || a->seq_len <= 0 || M % a->seq_len || a->rope_heads < 0 ||
         a->rope_heads > a->heads || !a->q || !a->k || !a->v)
       return fail(F5H_EINVAL, "op_gemm_epi: EPI_QKV needs N == 3 * heads * 64, M % seq_len == 0 and q, k, v");
+    if (a->qkv_dst_len != 0 && (a->qkv_dst_len < a->seq_len || a->ln_part_in))
+      return fail(F5H_EINVAL, "op_gemm_epi: qkv_dst_len must be 0 or >= seq_len, and takes no fold consumer");
+  } else if (a->qkv_dst_len) {
+    return fail(F5H_EINVAL, "op_gemm_epi: qkv_dst_len goes with EPI_QKV");
   } else if (!a->C) {
     return fail(F5H_EINVAL, "op_gemm_epi: null C");
   }
@@ -2538,7 +2893,17 @@ int f5h_op_gemm_epi(void* stream, const f5h_op_gemm_args* a, void* workspace, si
   const int Npad = (N + 127) / 128 * 128;
   // output element type: the operand dtype for these, fp32 otherwise
   const bool out_op = epi == EPI_GELU_TANH || epi == EPI_GELU_ERF_OP || epi == EPI_RESID16 || epi == EPI_STORE16;
-  const int64_t nC = (int64_t)(M + dual) * N, nA = (int64_t)M * K, nqkv = (int64_t)M * inner;
+  const int64_t nC = (int64_t)(M + dual) * N, nA = (int64_t)M * K;
+  // q / k / v elements the launch may address: M * inner, or with qkv_dst_len up to the end of its last panel's rows
+  int64_t nqkv = (int64_t)M * inner;
+  if (epi == EPI_QKV && a->qkv_dst_len) {
+    GemmArgs t{};
+    t.M = M;
+    t.heads = a->heads;
+    t.seq_len = a->seq_len;
+    t.qkv_dst_len = a->qkv_dst_len;
+    nqkv = (int64_t)qkv_dst_elems(t, M / a->seq_len);
+  }
   OpWs ws(workspace, workspace_bytes);
   void* wop = ws.take((size_t)Npad * K * es);
   void* aop = compute ? ws.take((size_t)nA * es) : nullptr;
@@ -2617,6 +2982,12 @@ int f5h_op_gemm_epi(void* stream, const f5h_op_gemm_args* a, void* workspace, si
     g.q_norm_w = a->q_norm_w;
     g.k_norm_w = a->k_norm_w;
     g.qk_norm_eps = a->qk_norm_eps;
+    g.qkv_dst_len = a->qkv_dst_len;
+    if (a->qkv_dst_len && compute) {  // rows the launch does not own come back as the caller's buffers hold them
+      HIPCK(f32_to_op(compute, a->q, nqkv, qop, st));
+      HIPCK(f32_to_op(compute, a->k, nqkv, kop, st));
+      HIPCK(f32_to_op(compute, a->v, nqkv, vop, st));
+    }
   }
   if (fold_prod) {
     // 0xFF bytes: NaN in fp32 and in both 16-bit types. Live rows: NaN with poison, else 0; guard rows: NaN

@@ -187,7 +187,7 @@ F5H_DEV void epi8(const GemmArgs& g, int row, int col, V8 x, const V8* pre = nul
       for (int e = 0; e < 8; ++e) x.v[e] = mul_nc(x.v[e], g.q_scale);
     }
     TC* dst = reinterpret_cast<TC*>(which == 0 ? g.q : (which == 1 ? g.k : g.v));
-    store8<TC>(dst + (((int64_t)s * g.heads + head) * g.seq_len + pos) * 64 + dh, x);
+    store8<TC>(dst + (((int64_t)s * g.heads + head) * qkv_panel_rows(g) + pos) * 64 + dh, x);
     return;
   }
   const int64_t off = (int64_t)row * g.ldc + col;
@@ -475,11 +475,12 @@ F5H_DEV void epilogue_fast_t(const GemmArgs& g, const f32x4 (&acc)[MT][NT], floa
     dh = hc & 63;
     rope_on = which < 2 && head < g.rope_heads;
     qsc = (which == 0 && g.q_scale != 0.f) ? g.q_scale : 1.f;
-    dst = rsrc_of(which == 0 ? g.q : (which == 1 ? g.k : g.v), (uint64_t)g.M * inner * sizeof(TC));
+    dst = rsrc_of(which == 0 ? g.q : (which == 1 ? g.k : g.v), qkv_dst_elems(g, g.qkv_dst_len ? fdiv(g.M, g.seq_len) : 0) * sizeof(TC));
   } else {
     constexpr int OES = (EPI == EPI_STORE || EPI == EPI_RESID || EPI == EPI_INPROJ) ? 4 : (int)sizeof(TC);
     dst = rsrc_of(g.C, (uint64_t)(g.M + (EPI == EPI_INPROJ ? g.dual_rows : 0)) * g.ldc * OES);
   }
+  const int dlen = EPI == EPI_QKV ? qkv_panel_rows(g) : 0;  // rows of a destination (sequence, head) panel
   // qk_norm: the [64] gain of this wave's q or k head, the lane's 8 columns loaded once (a v wave loads k's, unused)
   V8 qkw = V8{};
   if constexpr (QKN) qkw = load8((which == 0 ? g.q_norm_w : g.k_norm_w) + dh);
@@ -628,7 +629,7 @@ F5H_DEV void epilogue_fast_t(const GemmArgs& g, const f32x4 (&acc)[MT][NT], floa
           x.v[2 * p + 1] = r.y;
         }
         (void)row;
-        store8_rs<TC, AUX>(dst, (uint32_t)(((ps_sq[t] * g.heads + head) * g.seq_len + ps_pos[t]) * 64 + dh), x);
+        store8_rs<TC, AUX>(dst, (uint32_t)(((ps_sq[t] * g.heads + head) * dlen + ps_pos[t]) * 64 + dh), x);
         advance(ps_sq[t], ps_pos[t]);
       } else if constexpr (EPI == EPI_RESID || EPI == EPI_RESID16) {
         V8 c;
@@ -804,11 +805,12 @@ F5H_DEV void epilogue_direct_t(const GemmArgs& g, const f32x4 (&acc)[MT][NT], in
     for (int jp = 0; jp < NP; ++jp) dh[jp] = (colp[jp] - which * inner) & 63;
     rope_on = which < 2 && head < g.rope_heads;
     qsc = (which == 0 && g.q_scale != 0.f) ? g.q_scale : 1.f;
-    dst = rsrc_of(which == 0 ? g.q : (which == 1 ? g.k : g.v), (uint64_t)g.M * inner * sizeof(TC));
+    dst = rsrc_of(which == 0 ? g.q : (which == 1 ? g.k : g.v), qkv_dst_elems(g, g.qkv_dst_len ? fdiv(g.M, g.seq_len) : 0) * sizeof(TC));
   } else {
     constexpr int OES = (EPI == EPI_STORE || EPI == EPI_RESID || EPI == EPI_INPROJ) ? 4 : (int)sizeof(TC);
     dst = rsrc_of(g.C, (uint64_t)(g.M + (EPI == EPI_INPROJ ? g.dual_rows : 0)) * g.ldc * OES);
   }
+  const int dlen = EPI == EPI_QKV ? qkv_panel_rows(g) : 0;  // rows of a destination (sequence, head) panel
   // Loads only, raw bits, no arithmetic on their results here: conversions happen at the use, one strip
   // later (a branch or arithmetic on a just-loaded value makes hipcc wait for it, behind every older store).
   // Row indices are clamped instead of branched on (rows >= M are never stored).
@@ -916,7 +918,7 @@ F5H_DEV void epilogue_direct_t(const GemmArgs& g, const f32x4 (&acc)[MT][NT], in
           x.v[2 * p + 1] = rr.y;
         }
         (void)row;
-        store8_rs<TC, AUX>(dst, (uint32_t)(((ps_sq * g.heads + head) * g.seq_len + ps_pos) * 64 + dh[jp]), x);
+        store8_rs<TC, AUX>(dst, (uint32_t)(((ps_sq * g.heads + head) * dlen + ps_pos) * 64 + dh[jp]), x);
       } else if constexpr (EPI == EPI_RESID || EPI == EPI_RESID16) {
         V8 c;
         if constexpr (PREF)
@@ -2106,6 +2108,14 @@ static hipError_t launch_t(const GemmArgs& a, hipStream_t st) {
   const bool qkn = a.q_norm_w || a.k_norm_w;
   if (qkn && (EPI != EPI_QKV || !a.q_norm_w || !a.k_norm_w || a.heads <= 0 || a.N != 3 * a.heads * 64))
     return hipErrorInvalidValue;
+  // EPI_QKV into longer destination panels (qkv_dst_len): every configuration's epilogue addresses them; refused with
+  // a fold consumer (the engine never combines them), with panels shorter than the launch's sequences, and when a
+  // store offset could pass the 32-bit range of the strip epilogues' descriptors
+  if (a.qkv_dst_len) {
+    if (EPI != EPI_QKV || a.ln_part_in || a.seq_len <= 0 || a.qkv_dst_len < a.seq_len || a.M % a.seq_len ||
+        a.M >= (1 << 24) || a.heads <= 0 || qkv_dst_elems(a, a.M / a.seq_len) * 4 >= 0xF0000000ull)
+      return hipErrorInvalidValue;
+  }
   const bool strips = a.ln_part || a.ln_part_in || qkn;
   if (strips && (cfg == 12 || cfg == 13)) cfg = 11;
   // a 256x256 tile needs whole 256-column tiles for the strip epilogue: narrower outputs take the 128x128 tile

@@ -1,6 +1,7 @@
 // Launcher declarations for the engine's HIP kernels (gfx950).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace f5h {
@@ -83,7 +84,14 @@ struct GemmArgs {
   //   (mean_m, rstd_m) and applies x = rstd_m (acc - mean_m ln_u[n]) + ln_v[n] before the bias, where
   //   ln_u[n] = sum_k (1 + sc_k) W[n,k] and ln_v[n] = sum_k sh_k W[n,k] (lnfold_uv, per ODE step).
   void* hs; const float* hs_scale; float* ln_part;
-  const float* ln_part_in; int ln_nparts; const float* ln_u; const float* ln_v;
+  const float* ln_part_in; int ln_nparts;
+  // EPI_QKV: rows of a (sequence, head) panel in the destination, q / k / v [S, heads, qkv_dst_len, 64]; 0 = seq_len
+  // (the panels hold exactly the launch's rows). Larger: the launch fills rows [0, seq_len) of every panel and leaves
+  // the rest alone, so two launches (the second with q / k / v advanced by the first one's seq_len * 64 elements)
+  // fill one joint buffer without a copy (MMDiT: audio rows, then text rows). Not with a fold consumer. It sits in
+  // the alignment padding behind ln_nparts (see the layout note).
+  int qkv_dst_len;
+  const float* ln_u; const float* ln_v;
   // RMSNorm form (UNetT, x_transformers RMSNorm: x / max(|x|, 1e-12) sqrt(d) g): ln_rms = 1. The producer writes
   // (0, sum of squares) per strip and no hs (hs, hs_scale null); the consumer reads the residual stream itself as A,
   // its W already carries the gain (W' = W diag(g), built once), ln_u / ln_v are null (0) and rstd = 1 / sqrt(ss / d +
@@ -102,6 +110,19 @@ struct GemmArgs {
   const float* k_norm_w;
 };
 static_assert(sizeof(GemmArgs) == 304, "GemmArgs: keep the kernel argument's size (see the layout note)");
+static_assert(offsetof(GemmArgs, qkv_dst_len) == offsetof(GemmArgs, ln_nparts) + 4 &&
+                  offsetof(GemmArgs, ln_u) == offsetof(GemmArgs, ln_nparts) + 8,
+              "GemmArgs: qkv_dst_len fills the padding behind ln_nparts");
+
+// EPI_QKV destination panels (GemmArgs::qkv_dst_len): rows per panel, and the elements from q / k / v to the end of
+// the launch's last panel, which holds seq_len rows (the extent of the stores' buffer descriptors; rows >= M start a
+// panel past it and are dropped). qkv_dst_len == 0: M * heads * 64, as before.
+__host__ __device__ inline int qkv_panel_rows(const GemmArgs& g) { return g.qkv_dst_len ? g.qkv_dst_len : g.seq_len; }
+// (S = M / seq_len, the launch's sequences: the kernels pass their division-free quotient)
+__host__ __device__ inline uint64_t qkv_dst_elems(const GemmArgs& g, int S) {
+  if (!g.qkv_dst_len) return (uint64_t)g.M * g.heads * 64;
+  return ((uint64_t)(S * g.heads - 1) * g.qkv_dst_len + g.seq_len) * 64;
+}
 
 // Does the row tile [m0, m0 + BM) of an M-row GEMM hold a live row? Sequence s (rows [s*live_seq, (s+1)*live_seq))
 // contributes the tile's rows [max(m0, r0), min(last + 1, r0 + live_seq)); its live rows are [r0, r0 +
@@ -150,6 +171,11 @@ struct AttnArgs {
   DevProbe probe;         // in-kernel launch timing (null slots: off)
   int force_safe;         // test hook: every workgroup reruns its key loop in the lazy-max form (attention.hip)
   int store_wt;           // store policy: 1 = O is stored write-through (16-bit kernel), 0 = plain; attention_store_wt
+  // Split output (MMDiT joint attention; 0 = none): with 0 < o_split < L, row r < o_split of sequence s goes to
+  // o [S, o_split, H*64] and row r >= o_split to o2 [S, L - o_split, H*64] row r - o_split. Only the output
+  // addressing changes (the Q load, the K/V ring and the softmax see one sequence of L rows).
+  int o_split;
+  void* o2;
 };
 hipError_t attention(int compute, const AttnArgs& a, hipStream_t st);
 int attention_store_wt(int compute, const AttnArgs& a, int want);  // as gemm_store_wt
@@ -190,7 +216,8 @@ struct TextEmbArgs {
   const int64_t* text; int B, nt, N, td;
   const int32_t* seq_len;       // [B] per-sample valid length or null (= N for all)
   const float* table;           // [V, td]
-  const float* freqs;           // [8192, td] or null (no sinus pos)
+  const float* freqs;           // [8192, td] or null (no sinus pos); [freq_rows, td] when freq_rows > 0
+  int freq_rows;                // > 0: position n reads row min(n, freq_rows - 1) (MMDiT: 1024, mmdit.py:39-56)
   int mask_padding;
   float* out_c; float* out_u;   // [B, N, td] each
   uint8_t* keep;                // [2B*N] !fill (for masked_fill after each block) or null
@@ -298,6 +325,8 @@ hipError_t final_where_out(const float* cond, const uint8_t* cond_mask, const fl
 hipError_t ptr_upload(float* p, float** slot, hipStream_t st);
 // rowkeep[s*L + pos] = (pos - off < dur[s % B]) || pos < off ; for S sequences
 hipError_t build_rowkeep(const int32_t* dur, int B, int S, int L, int off, uint8_t* keep, hipStream_t st);
+// keep[s*nt + j] = text[(s % B)*nt + j] != -1 for S sequences (MMDiT c_mask, mmdit.py:232)
+hipError_t build_textkeep(const int64_t* text, int B, int S, int nt, uint8_t* keep, hipStream_t st);
 // kv_len[s] = dur[s % B] + off
 hipError_t build_kvlen(const int32_t* dur, int B, int S, int off, int32_t* kv, hipStream_t st);
 // h[s, 0, :] = temb (UNetT time token)

@@ -18,7 +18,8 @@ import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("F5H_LIB", os.path.join(_HERE, "lib", "libf5h.so"))
 
-F5H_DIT, F5H_UNETT = 0, 1
+F5H_DIT, F5H_UNETT, F5H_MMDIT = 0, 1, 2
+BACKBONE = {"DiT": F5H_DIT, "UNetT": F5H_UNETT, "MMDiT": F5H_MMDIT}
 F5H_FP32, F5H_BF16, F5H_FP16 = 0, 1, 2
 COMPUTE = {"fp32": F5H_FP32, "bf16": F5H_BF16, "fp16": F5H_FP16}
 F5H_DT_F32, F5H_DT_BF16, F5H_DT_F16 = 0, 1, 2
@@ -57,6 +58,7 @@ EXPORTS = (
     "f5h_op_linear",
     "f5h_op_attention",
     "f5h_op_attention_qlen",
+    "f5h_op_attention_split",
     "f5h_op_conv_pos",
     "f5h_op_norm",
     "f5h_op_dwconv_ln",
@@ -148,6 +150,8 @@ class OpGemmArgs(ctypes.Structure):
         ("poison", ctypes.c_int32),
         # qk_norm (both null: none)
         ("q_norm_w", ctypes.c_void_p), ("k_norm_w", ctypes.c_void_p), ("qk_norm_eps", ctypes.c_float),
+        # rows of a destination (sequence, head) panel (0 = seq_len); read by a library with has_mmdit()
+        ("qkv_dst_len", ctypes.c_int32),
     ]
 
 
@@ -236,6 +240,9 @@ def lib():
             L.f5h_op_lnfold_uv.restype = ctypes.c_int
             L.f5h_op_scale_cols.argtypes = [vp, i32, i64, i32, vp, vp, vp, vp, sz]
             L.f5h_op_scale_cols.restype = ctypes.c_int
+    if hasattr(L, "f5h_op_attention_split"):  # absent from an older build (has_mmdit)
+        L.f5h_op_attention_split.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, sz]
+        L.f5h_op_attention_split.restype = ctypes.c_int
     if hasattr(L, "f5h_op_text_upsample"):  # absent from an older build (has_dit_options)
         L.f5h_op_text_upsample.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp]
         L.f5h_op_text_upsample.restype = ctypes.c_int
@@ -301,6 +308,12 @@ def has_dit_options() -> bool:
     """False for an older build (F5H_LIB) without f5h_op_text_upsample: such a library ignores the arch fields
     qk_norm / long_skip_connection / text_average_upsampling and the qk_norm fields of the GEMM op hook."""
     return hasattr(lib(), "f5h_op_text_upsample")
+
+
+def has_mmdit() -> bool:
+    """False for an older build (F5H_LIB) without f5h_op_attention_split: such a library has no MMDiT backbone, no
+    split attention output and ignores the qkv_dst_len field of the GEMM op hook."""
+    return hasattr(lib(), "f5h_op_attention_split")
 
 
 def check(rc: int, what: str = "f5h"):

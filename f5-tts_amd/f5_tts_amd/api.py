@@ -16,9 +16,9 @@ import torch
 
 from . import configs, infer
 from .checkpoint import load_model
-from .model import CFM, DiT, UNetT
+from .model import CFM, DiT, MMDiT, UNetT
 
-_BACKBONES = {"DiT": DiT, "UNetT": UNetT}
+_BACKBONES = {"DiT": DiT, "UNetT": UNetT, "MMDiT": MMDiT}
 
 
 def seed_everything(seed: int = 0) -> None:

@@ -52,6 +52,22 @@ _UNETT_DEFAULTS = dict(
     skip_connect_type="concat",
 )
 
+# MMDiT.__init__ (mmdit.py:88-104): the text embedding has the model width, there are no ConvNeXt text blocks and every
+# head is rotated, so the dict carries the constructor's keys only (no text_dim / conv_layers / pe_attn_head)
+_MMDIT_DEFAULTS = dict(
+    backbone="MMDiT",
+    dim=1024,
+    depth=8,
+    heads=8,
+    dim_head=64,
+    ff_mult=4,
+    text_mask_padding=True,
+    qk_norm=None,
+    attn_mask_enabled=False,
+)
+
+_DEFAULTS = {"DiT": _DIT_DEFAULTS, "UNetT": _UNETT_DEFAULTS, "MMDiT": _MMDIT_DEFAULTS}
+
 PRESETS = {
     # F5TTS_v1_Base.yaml:24-37
     "F5TTS_v1_Base": dict(_DIT_DEFAULTS),
@@ -66,6 +82,8 @@ PRESETS = {
     # tiny configs used for golden vectors / quick parity (head dim stays 64: the engine's attention is Dh=64)
     "DiT_tiny": dict(_DIT_DEFAULTS, dim=128, depth=2, heads=2, text_dim=64, conv_layers=1),
     "UNetT_tiny": dict(_UNETT_DEFAULTS, dim=128, depth=4, heads=2),
+    # two full joint blocks and the context-pre-only last one (the reference ships no MMDiT config)
+    "MMDiT_tiny": dict(_MMDIT_DEFAULTS, dim=128, depth=3, heads=2, ff_mult=2),
 }
 
 
@@ -76,15 +94,60 @@ def get_arch(name_or_arch, **overrides) -> dict:
             raise KeyError(f"unknown preset {name_or_arch!r}; known: {sorted(PRESETS)}")
         arch = copy.deepcopy(PRESETS[name_or_arch])
     else:
-        base = _UNETT_DEFAULTS if name_or_arch.get("backbone", "DiT") == "UNetT" else _DIT_DEFAULTS
-        arch = dict(base)
+        arch = dict(_DEFAULTS.get(name_or_arch.get("backbone", "DiT"), _DIT_DEFAULTS))
         arch.update(name_or_arch)
     arch.update(overrides)
     arch.setdefault("text_num_embeds", VOCAB_SIZE)
     arch.setdefault("mel_dim", MEL_DIM)
-    if arch.get("text_dim") is None:
+    if arch["backbone"] != "MMDiT" and arch.get("text_dim") is None:
         arch["text_dim"] = arch["mel_dim"]
     return arch
+
+
+def _mmdit_param_shapes(arch: dict) -> "dict[str, tuple]":
+    """MMDiT (`mmdit.py:107-133`; blocks `modules.py:791-814`, joint attention `modules.py:398-427`), in the order of
+    the reference's state dict. The last block is context-pre-only: its `attn_norm_c` is an `AdaLayerNorm_Final`
+    (2d rows) and it has no `to_out_c` / `ff_c`."""
+    d = arch["dim"]
+    Dh = arch["dim_head"]
+    inner = arch["heads"] * Dh
+    F = int(d * arch["ff_mult"])
+    mel = arch["mel_dim"]
+    s = {}
+
+    def lin(p, n_out, n_in):
+        s[p + ".weight"] = (n_out, n_in)
+        s[p + ".bias"] = (n_out,)
+
+    lin("time_embed.time_mlp.0", d, 256)
+    lin("time_embed.time_mlp.2", d, d)
+    s["text_embed.text_embed.weight"] = (arch["text_num_embeds"] + 1, d)
+    lin("audio_embed.linear", d, 2 * mel)
+    for j in (0, 2):
+        s[f"audio_embed.conv_pos_embed.conv1d.{j}.weight"] = (d, d // 16, 31)
+        s[f"audio_embed.conv_pos_embed.conv1d.{j}.bias"] = (d,)
+    for i in range(arch["depth"]):
+        p = f"transformer_blocks.{i}."
+        last = i == arch["depth"] - 1
+        lin(p + "attn_norm_c.linear", (2 if last else 6) * d, d)
+        lin(p + "attn_norm_x.linear", 6 * d, d)
+        for c in ("", "_c"):
+            for n in ("to_q", "to_k", "to_v"):
+                lin(p + f"attn.{n}{c}", inner, d)
+            if arch.get("qk_norm"):
+                pre = "c_" if c else ""
+                s[p + f"attn.{pre}q_norm.weight"] = (Dh,)
+                s[p + f"attn.{pre}k_norm.weight"] = (Dh,)
+        lin(p + "attn.to_out.0", d, inner)
+        if not last:
+            lin(p + "attn.to_out_c", d, inner)
+            lin(p + "ff_c.ff.0.0", F, d)
+            lin(p + "ff_c.ff.2", d, F)
+        lin(p + "ff_x.ff.0.0", F, d)
+        lin(p + "ff_x.ff.2", d, F)
+    lin("norm_out.linear", 2 * d, d)
+    lin("proj_out", mel, d)
+    return s
 
 
 def param_shapes(arch: dict) -> "dict[str, tuple]":
@@ -95,6 +158,8 @@ def param_shapes(arch: dict) -> "dict[str, tuple]":
     and `unett.py:37-183`; the TRT converter's key map (`convert_checkpoint.py:129-145`)
     enumerates the same keys for the DiT.
     """
+    if arch["backbone"] == "MMDiT":
+        return _mmdit_param_shapes(arch)
     d = arch["dim"]
     H, Dh = arch["heads"], arch["dim_head"]
     inner = H * Dh

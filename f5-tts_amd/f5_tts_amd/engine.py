@@ -16,6 +16,8 @@ _VIEW_DT = {torch.float32: _lib.F5H_DT_F32, torch.bfloat16: _lib.F5H_DT_BF16, to
 
 
 def _arch_struct(arch: dict, compute: str) -> _lib.Arch:
+    if arch["backbone"] == "MMDiT":
+        return _mmdit_arch_struct(arch, compute)
     a = _lib.Arch()
     a.backbone = _lib.F5H_DIT if arch["backbone"] == "DiT" else _lib.F5H_UNETT
     a.dim = arch["dim"]
@@ -44,6 +46,46 @@ def _arch_struct(arch: dict, compute: str) -> _lib.Arch:
         raise RuntimeError("the loaded libf5h.so has no f5h_op_text_upsample (an older build): it would ignore qk_norm, "
                            "long_skip_connection and text_embedding_average_upsampling")
     return a
+
+
+def _mmdit_arch_struct(arch: dict, compute: str) -> _lib.Arch:
+    """MMDiT (mmdit.py:88-133): the text embedding has the model width, no ConvNeXt text blocks, RoPE on every head, no
+    DiT options. A dict that says otherwise is refused here, before any device work (the library checks the same)."""
+    d = arch["dim"]
+    for key, want in (("text_dim", d), ("conv_layers", 0), ("pe_attn_head", None), ("long_skip_connection", False),
+                      ("text_embedding_average_upsampling", False)):
+        have = arch.get(key, want)
+        if (have or None) != (want or None):
+            raise ValueError(f"MMDiT: {key} must be {want!r}, got {have!r}")
+    if arch["depth"] < 1:
+        raise ValueError(f"MMDiT: depth must be >= 1, got {arch['depth']}")
+    qk_norm = arch.get("qk_norm")
+    if qk_norm not in (None, "rms_norm"):
+        raise ValueError(f"Unimplemented qk_norm: {qk_norm}")  # as modules.py:408-409
+    if not _lib.has_mmdit():
+        raise RuntimeError("the loaded libf5h.so has no f5h_op_attention_split (an older build): it cannot run MMDiT")
+    a = _lib.Arch()
+    a.backbone = _lib.F5H_MMDIT
+    a.dim, a.depth, a.heads, a.dim_head = d, arch["depth"], arch["heads"], arch.get("dim_head", 64)
+    a.ff_dim = int(d * arch["ff_mult"])
+    a.text_dim = d
+    a.text_num_embeds, a.mel_dim = arch["text_num_embeds"], arch["mel_dim"]
+    a.text_mask_padding = int(bool(arch.get("text_mask_padding", True)))
+    a.attn_mask_enabled = int(bool(arch.get("attn_mask_enabled", False)))
+    a.compute = _lib.COMPUTE[compute]
+    a.qk_norm = 1 if qk_norm else 0
+    return a
+
+
+def _refuse_mmdit_masked(arch: dict, use_batch_mask) -> None:
+    """MMDiT with attn_mask_enabled and a batch mask (B > 1): the joint sequence's valid keys are [0, dur) and
+    [N, N + text length), not a prefix, and the attention kernel masks a suffix only. Refused before any device work
+    (f5h_sample / f5h_forward return F5H_EINVAL for the same call)."""
+    if arch["backbone"] == "MMDiT" and arch.get("attn_mask_enabled") and use_batch_mask:
+        raise NotImplementedError(
+            "MMDiT with attn_mask_enabled=True and a batch mask is not supported: the valid keys of the joint "
+            "text-audio sequence are not a prefix and the attention kernel masks a suffix only (DESIGN.md §8); "
+            "run single utterances, or the model without attn_mask_enabled")
 
 
 def _ode_method(method: str) -> int:
@@ -210,6 +252,7 @@ class Engine:
         y0 f32 [B,N,mel]; t_grid: host sequence of nfe+1 floats, the step grid. method: the fixed-grid
         solver, "euler", "midpoint" or "rk4" (1, 2, 4 backbone evaluations per step; f5h_sample_ode);
         the trajectory holds the nfe+1 grid points for every method."""
+        _refuse_mmdit_masked(self.arch, use_batch_mask)
         B, N, mel = cond.shape
         nt = text.shape[1]
         tg = np.ascontiguousarray(np.asarray(t_grid, dtype=np.float32))
@@ -260,6 +303,7 @@ class Engine:
         drop_audio_cond / drop_text. t: a python float, or a one-element device tensor (read on the
         stream, no host sync). text_cache: 0 = compute the text embedding for this call, 1 = compute
         and keep it in `workspace`, 2 = reuse the one kept there (dit.py:294-317)."""
+        _refuse_mmdit_masked(self.arch, use_batch_mask)
         B, N, mel = x.shape
         nt = text.shape[1]
         x = x.to(self.device, torch.float32).contiguous()
@@ -364,6 +408,31 @@ def op_attention(Q, K, V, kv_len=None, compute="bf16", q_prescaled=False, poison
     return (O, ws) if return_ws else O
 
 
+def op_attention_split(Q, K, V, o_split, kv_len=None, q_len=None, compute="bf16", q_prescaled=False, poison=False,
+                       return_ws=False):
+    """op_attention with the output split at row `o_split` (f5h_op_attention_split; MMDiT joint attention): returns
+    (O [S, o_split, H*64], O2 [S, N - o_split, H*64]). Both start as NaN; poison fills the workspace (16-bit q | k | v
+    | o | o2, back to back, 8 bytes per element of Q in all) with NaN bits first, so unwritten rows come back NaN in
+    every mode and the bytes past o2 show a write past either buffer. return_ws appends the workspace."""
+    if not _lib.has_mmdit():
+        raise RuntimeError("the loaded libf5h.so has no f5h_op_attention_split (an older build)")
+    S, H, N, D = Q.shape
+    assert D == 64 and 0 < o_split < N
+    O = torch.full((S, o_split, H * 64), float("nan"), dtype=torch.float32, device=Q.device)
+    O2 = torch.full((S, N - o_split, H * 64), float("nan"), dtype=torch.float32, device=Q.device)
+    ws = torch.empty(Q.numel() * 8 + 1024, dtype=torch.uint8, device=Q.device)
+    if poison:
+        ws.fill_(0xFF)
+    kv = None if kv_len is None else kv_len.to(Q.device, torch.int32).contiguous()
+    ql = None if q_len is None else q_len.to(Q.device, torch.int32).contiguous()
+    _lib.check(_lib.lib().f5h_op_attention_split(_lib.stream_handle(Q.device), _lib.COMPUTE[compute], S, H, N,
+                                                 Q.contiguous().data_ptr(), K.contiguous().data_ptr(),
+                                                 V.contiguous().data_ptr(), _lib.ptr(kv), _lib.ptr(ql),
+                                                 int(bool(q_prescaled)), int(o_split), O.data_ptr(), O2.data_ptr(),
+                                                 ws.data_ptr(), ws.numel()), "f5h_op_attention_split")
+    return (O, O2, ws) if return_ws else (O, O2)
+
+
 def _f32(t, dev=None):
     return None if t is None else t.to(device=dev or t.device, dtype=torch.float32).contiguous()
 
@@ -438,7 +507,7 @@ def op_gemm_epi(epi, A, W, bias=None, C=None, compute="bf16", A2=None, k_split=0
                 live_len=None, live_seq=0, add=None, dual_rows=0, seq_len=0, heads=0, rope_heads=0, q_scale=0.0,
                 hs_scale=None, ln_producer=False, ln_part_in=None, ln_u=None, ln_v=None, ln_rms=False, ln_eps=0.0,
                 ln_nparts=None, poison=False, ws_fill=None, return_ws=False, q_norm_w=None, k_norm_w=None,
-                qk_norm_eps=1e-6):
+                qk_norm_eps=1e-6, qkv_dst_len=0, qkv_bufs=None, qkv_row0=0):
     """A GEMM with epilogue `epi` (a key of EPI; f5h_op_gemm_epi). The in/out epilogues update a copy of C and
     return it; "inproj" returns C [M + dual_rows, N]; "qkv" returns (q, k, v [S,H,L,64], rope [L,32,2]).
 
@@ -450,7 +519,10 @@ def op_gemm_epi(epi, A, W, bias=None, C=None, compute="bf16", A2=None, k_split=0
     ws_fill: byte the workspace is filled with before the call; return_ws: the workspace is appended to the result
     (its buffers are taken in f5h_op_gemm_epi's order, each from a multiple of 256 bytes; the bytes past the last one
     are never written). q_norm_w, k_norm_w [64] ("qkv"): qk_norm = "rms_norm" with epsilon qk_norm_eps, the RMSNorm
-    of every q / k head after the bias and ahead of RoPE; both None: no norm."""
+    of every q / k head after the bias and ahead of RoPE; both None: no norm. qkv_dst_len ("qkv"; 0: none): the
+    destination panels hold qkv_dst_len rows, q / k / v are [S,H,qkv_dst_len,64] — qkv_bufs (q, k, v), updated in place,
+    or fresh NaN buffers — and the launch writes rows [qkv_row0, qkv_row0 + seq_len) of every panel (the pointers it
+    gets are advanced by qkv_row0 * 64 elements) and leaves the other rows alone."""
     M, K = A.shape
     N = W.shape[0]
     dev = A.device
@@ -482,11 +554,25 @@ def op_gemm_epi(epi, A, W, bias=None, C=None, compute="bf16", A2=None, k_split=0
     out = None
     if epi == "qkv":
         S = M // seq_len if seq_len > 0 else 0
-        q, k, v = (torch.full((S, heads, seq_len, 64), float("nan"), dtype=torch.float32, device=dev)
-                   for _ in range(3))
         rope = torch.empty(max(seq_len, 0), 32, 2, dtype=torch.float32, device=dev)
         a.seq_len, a.heads, a.rope_heads, a.q_scale = int(seq_len), int(heads), int(rope_heads), float(q_scale)
-        a.q, a.k, a.v, a.rope_out = q.data_ptr(), k.data_ptr(), v.data_ptr(), rope.data_ptr()
+        if qkv_dst_len:
+            if not _lib.has_mmdit():
+                raise RuntimeError("the loaded libf5h.so has no qkv_dst_len (an older build)")
+            assert 0 <= qkv_row0 and qkv_row0 + seq_len <= qkv_dst_len, "the launch's rows lie inside the panels"
+            q, k, v = qkv_bufs if qkv_bufs is not None else (
+                torch.full((S, heads, qkv_dst_len, 64), float("nan"), dtype=torch.float32, device=dev)
+                for _ in range(3))
+            for t in (q, k, v):
+                assert t.shape == (S, heads, qkv_dst_len, 64) and t.is_contiguous() and t.dtype == torch.float32
+            a.qkv_dst_len = int(qkv_dst_len)
+            off = int(qkv_row0) * 64 * 4
+            a.q, a.k, a.v, a.rope_out = q.data_ptr() + off, k.data_ptr() + off, v.data_ptr() + off, rope.data_ptr()
+            ws_bytes += 3 * S * heads * qkv_dst_len * 64 * 4
+        else:
+            q, k, v = (torch.full((S, heads, seq_len, 64), float("nan"), dtype=torch.float32, device=dev)
+                       for _ in range(3))
+            a.q, a.k, a.v, a.rope_out = q.data_ptr(), k.data_ptr(), v.data_ptr(), rope.data_ptr()
         if q_norm_w is not None or k_norm_w is not None:
             if not _lib.has_dit_options():
                 raise RuntimeError("the loaded libf5h.so has no qk_norm (an older build)")

@@ -112,6 +112,11 @@ class CFM(nn.Module):
         initial noise explicitly (parity tests), `keep_trajectory=False` skips the [steps+1,...] copy."""
         if self.training:
             self.eval()
+        arch = getattr(self.transformer, "arch", None)
+        if arch is not None:  # MMDiT with attn_mask_enabled and B > 1: refused before any device work
+            from ..engine import _refuse_mmdit_masked
+
+            _refuse_mmdit_masked(arch, cond.shape[0] > 1)
         pdtype = next(self.parameters()).dtype
         if cond.ndim == 2:  # raw wave -> mel (cfm.py:106-109)
             cond = self.mel_spec(cond)

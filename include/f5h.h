@@ -36,7 +36,18 @@ enum f5h_status {
   F5H_ENOMEM = -4,   /* workspace too small */
 };
 
-enum f5h_backbone { F5H_DIT = 0, F5H_UNETT = 1 };
+/* F5H_MMDIT (mmdit.py:87-262; a library that exports f5h_op_attention_split has it): joint text-audio attention.
+ * Audio tokens [S,N,d] and text tokens [S,nt,d] are two residual streams with their own AdaLN, QKV, out-projection and
+ * FFN weights; per block both are projected, rotated by RoPE independently (positions 0..N-1 and 0..nt-1), attended as
+ * one sequence of N + nt rows and split again. The last block only pre-normalises the text stream (context_pre_only).
+ * The arch must have text_dim == dim, conv_layers == 0, pe_attn_head == 0, long_skip_connection == 0,
+ * text_average_upsampling == 0 and depth >= 1 (F5H_EINVAL names the field); qk_norm adds c_q_norm / c_k_norm.
+ * nt >= 1. attn_mask_enabled together with use_batch_mask is refused by f5h_sample / f5h_forward (F5H_EINVAL): the
+ * valid keys [0, dur) and [N, N + tlen) are not a prefix of the joint sequence; without a batch mask
+ * the flag has no effect, as in the reference. Accepted without effect on such an engine: f5h_set_chain,
+ * f5h_set_ln_fold, f5h_set_pad_skip and f5h_set_cfg_streams (the joint layout has no live-row prefix, and the block
+ * step always runs as one chain of separate launches). */
+enum f5h_backbone { F5H_DIT = 0, F5H_UNETT = 1, F5H_MMDIT = 2 };
 /* Operand dtype of the GEMM / attention / conv MFMAs. Accumulation, norm and softmax statistics and
  * the ODE state are fp32 in every mode; the residual stream is fp32 in the fp32 mode and, in the 16-bit
  * modes, kept in the operand dtype on both backbones (DiT and UNetT), as the reference keeps it in the
@@ -327,6 +338,16 @@ int f5h_op_attention_qlen(void* stream, int32_t compute, int32_t S, int32_t H, i
                           const float* K, const float* V, const int32_t* kv_len, const int32_t* q_len,
                           int32_t q_prescaled, float* O, void* workspace, size_t workspace_bytes);
 
+/* f5h_op_attention_qlen with a split output (MMDiT joint attention): with 0 < o_split < N, row r < o_split of
+ * sequence s goes to O [S, o_split, H*64] and row r >= o_split to O2 [S, N - o_split, H*64] row r - o_split; o_split
+ * == 0 is f5h_op_attention_qlen (O2 unused). In the 16-bit modes the 16-bit O and O2 sit back to back at workspace
+ * byte 6 * S*H*N*64 (S*H*N*64 elements together) and are then converted whole, as f5h_op_attention_qlen's. Its
+ * presence tells a caller that the library runs F5H_MMDIT engines and reads f5h_op_gemm_args.qkv_dst_len. */
+int f5h_op_attention_split(void* stream, int32_t compute, int32_t S, int32_t H, int32_t N, const float* Q,
+                           const float* K, const float* V, const int32_t* kv_len, const int32_t* q_len,
+                           int32_t q_prescaled, int32_t o_split, float* O, float* O2, void* workspace,
+                           size_t workspace_bytes);
+
 /* Op-level entry points of the conv, norm and GEMM-epilogue kernels (tests/test_gpu_ops.py). fp32 device tensors
  * in and out; buffers a kernel reads or writes in the operand dtype are staged in `workspace` (rounded to nearest
  * even); the production launcher runs unchanged. A buffer the kernel writes in the operand dtype starts as the
@@ -421,6 +442,11 @@ typedef struct f5h_op_gemm_args {
   const float* q_norm_w;
   const float* k_norm_w;
   float qk_norm_eps;
+  /* epi 7 (read by a library that exports f5h_op_attention_split): rows of a destination (sequence, head) panel, 0 =
+   * seq_len. Larger: q, k, v are [M/seq_len, heads, qkv_dst_len, 64], the launch writes rows [0, seq_len) of every panel
+   * and leaves the others as the caller's buffers hold them (the hook pre-fills its 16-bit staging from them). Refused
+   * below seq_len and with a fold consumer. */
+  int32_t qkv_dst_len;
 } f5h_op_gemm_args;
 #define F5H_OP_GUARD_ROWS 4
 int f5h_op_gemm_epi(void* stream, const f5h_op_gemm_args* args, void* workspace, size_t workspace_bytes);
