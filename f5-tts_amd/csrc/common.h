@@ -181,6 +181,18 @@ F5H_DEV float wave_max(float v) {
   return v;
 }
 
+// ---------------------------------------------------------------- ragged batches (packed rows)
+// Utterance s of a packed batch owns rows [off[s], off[s+1]), off[0] = 0, every length >= 1: the
+// segment of row r (0 <= r < off[B]) is the last s with off[s] <= r.
+F5H_DEV int seg_find(const int* off, int B, int r) {
+  int lo = 0, hi = B;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (off[mid] <= r) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
 // ---------------------------------------------------------------- LDS swizzle
 // Tiles are stored as rows of 128 bytes = 8 chunks of 16 B. Chunk c of row r lives at
 // c ^ g(r), g(r) = ((r>>1)&1)<<2 | ((r>>2)&3): conflict-free for ds_read_b128 where the

@@ -72,6 +72,25 @@ hipError_t grid_upload(const float* t_host, int n, float* out, hipStream_t st) {
   hipLaunchKernelGGL(grid_upload_kernel, dim3(nblk(n, 256)), dim3(256), 0, st, tv, n, out);
   return hipGetLastError();
 }
+// Host int32 values into a device array, 512 per launch as the kernel-argument payload (2 KB): stream-ordered
+// without a staging buffer, and the host array is free as soon as the call returns.
+struct IVals {
+  int32_t v[512];
+};
+__global__ void seg_upload_kernel(IVals iv, int n, int32_t* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = iv.v[i];
+}
+hipError_t seg_upload(const int32_t* host, int64_t n, int32_t* out, hipStream_t st) {
+  if (n <= 0 || !host || !out) return hipErrorInvalidValue;
+  for (int64_t o = 0; o < n; o += 512) {
+    const int m = (int)(n - o < 512 ? n - o : 512);
+    IVals iv{};
+    for (int i = 0; i < m; ++i) iv.v[i] = host[o + i];
+    hipLaunchKernelGGL(seg_upload_kernel, dim3(nblk(m, 256)), dim3(256), 0, st, iv, m, out + o);
+  }
+  return hipGetLastError();
+}
 
 // ---------------------------------------------------------------- NFE-step bookkeeping
 // One NFE step is a fixed launch sequence (hipGraph-replayable): step_begin copies the step's
@@ -559,13 +578,11 @@ hipError_t text_upsample(const TextUpArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-// ConvNeXtV2Block front half (modules.py:260-264): depthwise Conv1d(k7, pad3) + bias -> LayerNorm(affine)
+// ConvNeXtV2Block front half (modules.py:260-264): depthwise Conv1d(k7, pad3) + bias -> LayerNorm(affine).
+// One wave per row: row n of a sequence of L rows that starts at row `base` of x (taps outside [0, L) are zero).
 template <typename TO>
-__global__ void dwconv_ln_kernel(const float* x, int S, int L, int C, const float* w, const float* bias,
-                                 const float* lw, const float* lb, TO* out) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= S * L) return;
-  const int s = row / L, n = row - s * L;
+F5H_DEV void dwconv_ln_row(const float* x, int64_t base, int n, int L, int C, const float* w, const float* bias,
+                           const float* lw, const float* lb, TO* out, int lane) {
   float v[16];  // C <= 1024
   float sum = 0.f;
 #pragma unroll
@@ -577,7 +594,7 @@ __global__ void dwconv_ln_kernel(const float* x, int S, int L, int C, const floa
 #pragma unroll
       for (int t = 0; t < 7; ++t) {
         int q = n + t - 3;
-        if (q >= 0 && q < L) acc += w[c * 7 + t] * x[((int64_t)s * L + q) * C + c];
+        if (q >= 0 && q < L) acc += w[c * 7 + t] * x[(base + q) * C + c];
       }
     }
     v[k] = acc;
@@ -594,13 +611,37 @@ __global__ void dwconv_ln_kernel(const float* x, int S, int L, int C, const floa
 #pragma unroll
   for (int k = 0; k < 16; ++k) {
     int c = lane + 64 * k;
-    if (c < C) out[(int64_t)row * C + c] = from_f32<TO>((v[k] - mean) * rstd * lw[c] + lb[c]);
+    if (c < C) out[(base + n) * C + c] = from_f32<TO>((v[k] - mean) * rstd * lw[c] + lb[c]);
   }
+}
+template <typename TO>
+__global__ void dwconv_ln_kernel(const float* x, int S, int L, int C, const float* w, const float* bias,
+                                 const float* lw, const float* lb, TO* out) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= S * L) return;
+  const int s = row / L, n = row - s * L;
+  dwconv_ln_row<TO>(x, (int64_t)s * L, n, L, C, w, bias, lw, lb, out, lane);
 }
 hipError_t dwconv_ln(int compute, const float* x, int S, int L, int C, const float* dw_w, const float* dw_b,
                      const float* ln_w, const float* ln_b, void* out, hipStream_t st) {
   if (C > 1024) return hipErrorInvalidValue;
   F5H_OP_DISPATCH(compute, T, hipLaunchKernelGGL(dwconv_ln_kernel<T>, dim3(nblk(S * L, 4)), dim3(256), 0, st, x, S, L, C, dw_w, dw_b, ln_w, ln_b, (T*)out););
+  return hipGetLastError();
+}
+// The same over packed rows of unequal sequences (kernels.h, ragged batches): the row's sequence comes from the
+// segment table, and the arithmetic per row is dwconv_ln_row's, so each sequence has dwconv_ln's bits.
+template <typename TO>
+__global__ void dwconv_ln_ragged_kernel(const float* x, const int* off, int B, int R, int C, const float* w,
+                                        const float* bias, const float* lw, const float* lb, TO* out) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= R) return;
+  const int s = seg_find(off, B, row), base = off[s];
+  dwconv_ln_row<TO>(x, base, row - base, off[s + 1] - base, C, w, bias, lw, lb, out, lane);
+}
+hipError_t dwconv_ln_ragged(int compute, const float* x, const int32_t* off, int B, int R, int C, const float* dw_w,
+                            const float* dw_b, const float* ln_w, const float* ln_b, void* out, hipStream_t st) {
+  if (C > 1024 || B <= 0 || R <= 0) return hipErrorInvalidValue;
+  F5H_OP_DISPATCH(compute, T, hipLaunchKernelGGL(dwconv_ln_ragged_kernel<T>, dim3(nblk(R, 4)), dim3(256), 0, st, x, off, B, R, C, dw_w, dw_b, ln_w, ln_b, (T*)out););
   return hipGetLastError();
 }
 

@@ -343,6 +343,30 @@ hipError_t vocos_ola(const float* frames, const float* win, int B, int T, int n_
 hipError_t mel_frames(const float* wav, int B, int L, int T, int n_fft, int hop, float* frames, hipStream_t st);
 hipError_t mel_mag(const float* spec, int64_t rows, int bins, int ld_spec, int ld_mag, float* mag, hipStream_t st);
 hipError_t mel_log(const float* mel, int B, int T, int n_mels, float* out, hipStream_t st);
+// ---- Ragged batches: B utterances of unequal length as packed rows, no padding rows. A device segment table
+// int32 off[B + 1] (off[0] = 0, utterance s owns rows [off[s], off[s+1]), every length >= 1) tells the four kernels
+// with a reach across rows where each utterance begins and ends; the row-local kernels run on M = off[B] rows.
+// Each result equals the per-utterance kernel's bit for bit (same operations in the same order per element).
+// host int32 values -> device (by kernel argument, stream-ordered: the host array is free on return)
+hipError_t seg_upload(const int32_t* host, int64_t n, int32_t* out, hipStream_t st);
+// dwconv_ln over packed rows x [R, C]: taps outside the row's own segment are zero
+hipError_t dwconv_ln_ragged(int compute, const float* x, const int32_t* off, int B, int R, int C, const float* dw_w,
+                            const float* dw_b, const float* ln_w, const float* ln_b, void* out, hipStream_t st);
+// vocos_im2col from a strided source: packed row off[s] + t reads src[s*row_st + (start[s] + t + j - 3)*frame_st +
+// c*chan_st] (element strides), zero for taps outside [0, off[s+1] - off[s])
+hipError_t vocos_im2col_ragged(int compute, const float* src, int64_t row_st, int64_t frame_st, int64_t chan_st,
+                               const int32_t* off, const int32_t* start, int B, int R, int C, int Kp, void* out,
+                               hipStream_t st);
+// vocos_ola per segment: y packed, utterance s at (off[s] - s)*hop, (len_s - 1)*hop samples
+hipError_t vocos_ola_ragged(const float* frames, const float* win, const int32_t* off, int B, int R, int n_fft,
+                            int hop, float* y, hipStream_t st);
+// mel_frames with one length per wave: off = frame offsets (T_s = 1 + len[s]/hop), wav row s at s*wav_st,
+// reflection at len[s] (every len[s] > n_fft/2, checked by the caller)
+hipError_t mel_frames_ragged(const float* wav, int64_t wav_st, const int32_t* off, const int32_t* len, int B, int R,
+                             int n_fft, int hop, float* frames, hipStream_t st);
+// out[s][t][m] = log(max(mel[off[s] + t][m], 1e-5)) for t < T_s, exact 0 for T_s <= t < T_out ([B, T_out, n_mels])
+hipError_t mel_log_ragged(const float* mel, const int32_t* off, int B, int T_out, int n_mels, float* out,
+                          hipStream_t st);
 hipError_t f32_to_op(int compute, const float* x, int64_t n, void* out, hipStream_t st);
 hipError_t op_to_f32(int compute, const void* x, int64_t n, float* out, hipStream_t st);
 // Weight packing (engine creation): dst[i0*dst_st[0] + i1*dst_st[1] + i2*dst_st[2] + i3] =

@@ -84,6 +84,35 @@ size_t mlayout(const f5h_mel* m, int B, int T, char* base, MBufs* b) {
 
 }  // namespace
 
+// The row-local middle on R frame rows (b.frames filled): DFT GEMM -> |X| -> filterbank GEMM -> b.melb [R][n_mels]
+static int mel_rows(f5h_mel* m, const MBufs& b, int R, hipStream_t st) {
+  const int nf = m->a.n_fft;
+  GemmArgs g{};
+  g.A = b.frames;
+  g.lda = nf;
+  g.W = m->dft;
+  g.ldw = nf;
+  g.M = R;
+  g.N = 2 * m->bins;
+  g.K = nf;
+  g.C = b.spec;
+  g.ldc = m->ks;
+  MHIP(gemm(0, EPI_STORE, g, st));
+  MHIP(mel_mag(b.spec, R, m->bins, m->ks, m->km, b.mag, st));
+  GemmArgs f{};
+  f.A = b.mag;
+  f.lda = m->km;
+  f.W = m->fb;
+  f.ldw = m->km;
+  f.M = R;
+  f.N = m->a.n_mels;
+  f.K = m->km;
+  f.C = b.melb;
+  f.ldc = m->a.n_mels;
+  MHIP(gemm(0, EPI_STORE, f, st));
+  return 0;
+}
+
 int f5h_mel_create(const f5h_mel_arch* arch, int32_t device, f5h_mel** out) {
   if (!arch || !out) return f5h_internal_fail(F5H_EINVAL, "null argument");
   *out = nullptr;
@@ -164,31 +193,66 @@ int f5h_mel_forward(f5h_mel* m, void* stream, int32_t B, int32_t L, const float*
   MHIP(hipSetDevice(m->dev));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   f5h::UseNote used{m->uses, st};
-  const int R = B * T, nf = m->a.n_fft;
-  MHIP(mel_frames(wav, B, L, T, nf, m->a.hop_length, b.frames, st));
-  GemmArgs g{};
-  g.A = b.frames;
-  g.lda = nf;
-  g.W = m->dft;
-  g.ldw = nf;
-  g.M = R;
-  g.N = 2 * m->bins;
-  g.K = nf;
-  g.C = b.spec;
-  g.ldc = m->ks;
-  MHIP(gemm(0, EPI_STORE, g, st));
-  MHIP(mel_mag(b.spec, R, m->bins, m->ks, m->km, b.mag, st));
-  GemmArgs f{};
-  f.A = b.mag;
-  f.lda = m->km;
-  f.W = m->fb;
-  f.ldw = m->km;
-  f.M = R;
-  f.N = m->a.n_mels;
-  f.K = m->km;
-  f.C = b.melb;
-  f.ldc = m->a.n_mels;
-  MHIP(gemm(0, EPI_STORE, f, st));
+  MHIP(mel_frames(wav, B, L, T, m->a.n_fft, m->a.hop_length, b.frames, st));
+  const int rc = mel_rows(m, b, B * T, st);
+  if (rc) return rc;
   MHIP(mel_log(b.melb, B, T, m->a.n_mels, mel, st));
+  return 0;
+}
+
+// ragged workspace: the segment table (frame offsets [B + 1], wave lengths [B]) then the buffers of R frames
+static size_t mlayout_ragged(const f5h_mel* m, int B, int64_t R, char* base, int32_t** tab, MBufs* b) {
+  const size_t tbytes = ((2 * (size_t)B + 1) * sizeof(int32_t) + 255) / 256 * 256;
+  if (tab) *tab = reinterpret_cast<int32_t*>(base);
+  return tbytes + mlayout(m, 1, (int)R, base ? base + tbytes : nullptr, b);
+}
+
+size_t f5h_mel_ragged_workspace_size(const f5h_mel* m, int32_t B, int64_t total_frames) {
+  if (!m || B <= 0 || total_frames < B || total_frames > (1 << 24)) return 0;
+  MBufs b;
+  return mlayout_ragged(m, B, total_frames, nullptr, nullptr, &b);
+}
+
+int f5h_mel_forward_ragged(f5h_mel* m, void* stream, int32_t B, const float* wav, int64_t wav_stride,
+                           const int32_t* lens, int32_t T_out, float* cond, void* workspace, size_t workspace_bytes) {
+  if (!m) return f5h_internal_fail(F5H_EINVAL, "null mel");
+  if (B <= 0 || B > (1 << 24)) return f5h_internal_fail(F5H_EINVAL, "bad B");
+  if (!wav || !lens || !cond || !workspace) return f5h_internal_fail(F5H_EINVAL, "null tensor argument");
+  const int hop = m->a.hop_length;
+  std::vector<int32_t> tab(2 * (size_t)B + 1);
+  int64_t R = 0;
+  for (int i = 0; i < B; ++i) {
+    if (lens[i] <= m->a.n_fft / 2)
+      return f5h_internal_fail(F5H_EINVAL, "forward_ragged: wave " + std::to_string(i) + " has " +
+                                               std::to_string(lens[i]) + " samples (L must exceed n_fft/2 = " +
+                                               std::to_string(m->a.n_fft / 2) + ")");
+    const int T = 1 + lens[i] / hop;
+    if (T > T_out)
+      return f5h_internal_fail(F5H_EINVAL, "forward_ragged: wave " + std::to_string(i) + " has " + std::to_string(T) +
+                                               " frames, T_out is " + std::to_string(T_out));
+    tab[i] = (int32_t)R;
+    tab[B + 1 + i] = lens[i];
+    R += T;
+    if (R > (1 << 24))
+      return f5h_internal_fail(F5H_EINVAL, "forward_ragged: more than 2^24 frames in all (reached at wave " +
+                                               std::to_string(i) + ")");
+  }
+  tab[B] = (int32_t)R;
+  if ((int64_t)B * T_out > (1 << 24)) return f5h_internal_fail(F5H_EINVAL, "forward_ragged: B * T_out above 2^24");
+  MBufs b;
+  int32_t* off = nullptr;
+  const size_t need = mlayout_ragged(m, B, R, nullptr, nullptr, &b);
+  if (workspace_bytes < need)
+    return f5h_internal_fail(F5H_ENOMEM, "mel workspace too small: need " + std::to_string(need));
+  mlayout_ragged(m, B, R, reinterpret_cast<char*>(workspace), &off, &b);
+  MHIP(hipSetDevice(m->dev));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  f5h::UseNote used{m->uses, st};
+  // the table travels as kernel arguments: nothing waits and the caller's array is not read after this call
+  MHIP(seg_upload(tab.data(), (int64_t)tab.size(), off, st));
+  MHIP(mel_frames_ragged(wav, wav_stride, off, off + B + 1, B, (int)R, m->a.n_fft, hop, b.frames, st));
+  const int rc = mel_rows(m, b, (int)R, st);
+  if (rc) return rc;
+  MHIP(mel_log_ragged(b.melb, off, B, T_out, m->a.n_mels, cond, st));
   return 0;
 }

@@ -67,4 +67,48 @@ hipError_t mel_log(const float* mel, int B, int T, int n_mels, float* out, hipSt
   return hipGetLastError();
 }
 
+// ---- Ragged batch (kernels.h): waves of unequal length, frames packed (wave s owns frame rows
+// [off[s], off[s+1]), T_s = 1 + len[s]/hop). Zero-padding the waves to one length is not equivalent: the last
+// frames of a wave must reflect at its own end, not read the padding.
+
+// mel_frames with the reflection at each wave's own length
+__global__ void mel_frames_ragged_kernel(const float* wav, int64_t wav_st, const int* off, const int* len, int B,
+                                         int R, int n_fft, int hop, float* frames) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)R * n_fft) return;
+  const int j = (int)(i % n_fft), r = (int)(i / n_fft);
+  const int s = seg_find(off, B, r), L = len[s];
+  int p = (r - off[s]) * hop + j - n_fft / 2;
+  if (p < 0) p = -p;
+  if (p >= L) p = 2 * (L - 1) - p;
+  frames[i] = wav[s * wav_st + p];
+}
+hipError_t mel_frames_ragged(const float* wav, int64_t wav_st, const int32_t* off, const int32_t* len, int B, int R,
+                             int n_fft, int hop, float* frames, hipStream_t st) {
+  if (B <= 0 || R < B) return hipErrorInvalidValue;
+  const int64_t n = (int64_t)R * n_fft;
+  hipLaunchKernelGGL(mel_frames_ragged_kernel, dim3(mblk(n, 256)), dim3(256), 0, st, wav, wav_st, off, len, B, R,
+                     n_fft, hop, frames);
+  return hipGetLastError();
+}
+
+// out[s][t][m] = log(max(mel[off[s] + t][m], 1e-5)) for t < T_s and exact zeros up to T_out: the frame-major
+// [B, T_out, n_mels] conditioning CFM.sample takes, equal to zero-padding the per-wave log-mels
+__global__ void mel_log_ragged_kernel(const float* mel, const int* off, int B, int T_out, int n_mels, float* out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)B * T_out * n_mels) return;
+  const int m = (int)(i % n_mels);
+  const int64_t st = i / n_mels;
+  const int t = (int)(st % T_out), s = (int)(st / T_out);
+  const int base = off[s];
+  out[i] = t < off[s + 1] - base ? logf(fmaxf(mel[((int64_t)base + t) * n_mels + m], 1e-5f)) : 0.f;
+}
+hipError_t mel_log_ragged(const float* mel, const int32_t* off, int B, int T_out, int n_mels, float* out,
+                          hipStream_t st) {
+  if (B <= 0 || T_out <= 0) return hipErrorInvalidValue;
+  const int64_t n = (int64_t)B * T_out * n_mels;
+  hipLaunchKernelGGL(mel_log_ragged_kernel, dim3(mblk(n, 256)), dim3(256), 0, st, mel, off, B, T_out, n_mels, out);
+  return hipGetLastError();
+}
+
 }  // namespace f5h

@@ -11,6 +11,8 @@
 //   frames [R][n_fft]     fp32            windowed irfft frames (iDFT GEMM output)
 // The iDFT is a GEMM against a fixed basis [n_fft][Kd] (window and irfft weights folded in,
 // fp32 MFMA), followed by a deterministic overlap-add that divides by the window envelope.
+// f5h_vocos_decode_ragged runs B utterances of unequal length as R = sum len_i packed rows of the same
+// buffers, behind a segment table int32 [off[B+1] | start[B]] at the head of the workspace (kernels.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -271,6 +273,37 @@ GemmArgs vg(const void* A, int64_t lda, const VLin& W, int M, void* C, int64_t l
     if (_e != hipSuccess) return f5h_internal_fail(F5H_EHIP, std::string(#x) + ": " + hipGetErrorString(_e)); \
   } while (0)
 
+// The network after the embed im2col (b.col filled), on R packed rows: B sequences of T rows each (off null), or
+// the ragged batch of the device segment table off[B + 1]. Only the depthwise conv and the overlap-add reach
+// across rows; everything else is row-local and the same launch in both forms.
+static int vnet(f5h_vocos* v, const VBufs& b, hipStream_t st, int B, int T, const int32_t* off, int R, float* audio) {
+  const f5h_vocos_arch& a = v->a;
+  const int d = a.dim, I = a.intermediate_dim, bf = v->bf;
+  // backbone (vocos VocosBackbone.forward): embed -> LayerNorm -> ConvNeXt blocks -> final LayerNorm
+  VK(gemm(bf, EPI_STORE, vg(b.col, v->kemb, v->embed, R, b.x0, d), st));
+  VK(ln_modulate(0, b.x0, 0, R, d, v->norm_b, v->norm_sm1, b.x, st));
+  for (const VBlock& blk : v->blocks) {
+    if (off)
+      VK(dwconv_ln_ragged(bf, b.x, off, B, R, d, blk.dw_w, blk.dw_b, blk.ln_w, blk.ln_b, b.dwln, st));
+    else
+      VK(dwconv_ln(bf, b.x, B, T, d, blk.dw_w, blk.dw_b, blk.ln_w, blk.ln_b, b.dwln, st));
+    VK(gemm(bf, EPI_GELU_ERF_OP, vg(b.dwln, d, blk.pw1, R, b.hid, I), st));
+    GemmArgs g = vg(b.hid, I, blk.pw2, R, b.x, d);
+    g.gate = blk.gamma;  // x += gamma * pwconv2(.)
+    VK(gemm(bf, EPI_RESID, g, st));
+  }
+  VK(ln_modulate(0, b.x, 0, R, d, v->fnorm_b, v->fnorm_sm1, b.fln, st));
+  // head (ISTFTHead.forward), fp32: Linear -> (mag, phase) -> (re, im) -> iDFT frames -> overlap-add
+  VK(gemm(0, EPI_STORE, vg(b.fln, d, v->head, R, b.spec, v->kd), st));
+  VK(vocos_spec(b.spec, R, v->bins, v->kd, st));
+  VK(gemm(0, EPI_STORE, vg(b.spec, v->kd, v->idft, R, b.frames, a.n_fft), st));
+  if (off)
+    VK(vocos_ola_ragged(b.frames, v->win, off, B, R, a.n_fft, a.hop_length, audio, st));
+  else
+    VK(vocos_ola(b.frames, v->win, B, T, a.n_fft, a.hop_length, audio, st));
+  return 0;
+}
+
 int f5h_vocos_create(const f5h_vocos_arch* arch, const f5h_weight* weights, int32_t n_weights, int32_t device,
                      f5h_vocos** out) {
   if (!out || !arch || (n_weights > 0 && !weights)) return f5h_internal_fail(F5H_EINVAL, "null argument");
@@ -344,24 +377,60 @@ int f5h_vocos_decode(f5h_vocos* v, void* stream, int32_t B, int32_t T, const flo
   VHIP(hipSetDevice(v->dev));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   f5h::UseNote used{v->uses, st};
-  const f5h_vocos_arch& a = v->a;
-  const int R = B * T, d = a.dim, I = a.intermediate_dim, bf = v->bf;
-  // backbone (vocos VocosBackbone.forward): embed -> LayerNorm -> ConvNeXt blocks -> final LayerNorm
-  VK(vocos_im2col(bf, mel, B, T, a.input_channels, v->kemb, b.col, st));
-  VK(gemm(bf, EPI_STORE, vg(b.col, v->kemb, v->embed, R, b.x0, d), st));
-  VK(ln_modulate(0, b.x0, 0, R, d, v->norm_b, v->norm_sm1, b.x, st));
-  for (const VBlock& blk : v->blocks) {
-    VK(dwconv_ln(bf, b.x, B, T, d, blk.dw_w, blk.dw_b, blk.ln_w, blk.ln_b, b.dwln, st));
-    VK(gemm(bf, EPI_GELU_ERF_OP, vg(b.dwln, d, blk.pw1, R, b.hid, I), st));
-    GemmArgs g = vg(b.hid, I, blk.pw2, R, b.x, d);
-    g.gate = blk.gamma;  // x += gamma * pwconv2(.)
-    VK(gemm(bf, EPI_RESID, g, st));
+  VK(vocos_im2col(v->bf, mel, B, T, v->a.input_channels, v->kemb, b.col, st));
+  return vnet(v, b, st, B, T, nullptr, B * T, audio);
+}
+
+size_t f5h_vocos_ragged_workspace_size(const f5h_vocos* v, int32_t B, int64_t total_frames) {
+  if (!v || B <= 0 || total_frames < B || total_frames > (1 << 24)) return 0;
+  VWS ws;
+  VBufs b;
+  ws.take<int32_t>(2 * (size_t)B + 1);
+  vlayout(v, ws, b, 1, (int)total_frames);
+  return ws.off;
+}
+
+int f5h_vocos_decode_ragged(f5h_vocos* v, void* stream, int32_t B, const float* feats, int64_t row_stride,
+                            int64_t frame_stride, int64_t chan_stride, const int32_t* starts, const int32_t* lens,
+                            float* audio_packed, void* workspace, size_t workspace_bytes) {
+  if (!v) return f5h_internal_fail(F5H_EINVAL, "null vocos");
+  if (B <= 0 || B > (1 << 24)) return f5h_internal_fail(F5H_EINVAL, "bad B");
+  if (!feats || !starts || !lens || !workspace) return f5h_internal_fail(F5H_EINVAL, "null tensor argument");
+  // segment table (host): off[B + 1] packed row offsets, then start[B]
+  std::vector<int32_t> tab(2 * (size_t)B + 1);
+  int64_t R = 0;
+  for (int i = 0; i < B; ++i) {
+    if (lens[i] < 1)
+      return f5h_internal_fail(F5H_EINVAL, "decode_ragged: row " + std::to_string(i) + " has length " +
+                                               std::to_string(lens[i]) + " (at least 1 frame)");
+    if (starts[i] < 0)
+      return f5h_internal_fail(F5H_EINVAL, "decode_ragged: row " + std::to_string(i) + " has a negative start " +
+                                               std::to_string(starts[i]));
+    tab[i] = (int32_t)R;
+    tab[B + 1 + i] = starts[i];
+    R += lens[i];
+    if (R > (1 << 24))
+      return f5h_internal_fail(F5H_EINVAL, "decode_ragged: more than 2^24 frames in all (reached at row " +
+                                               std::to_string(i) + ")");
   }
-  VK(ln_modulate(0, b.x, 0, R, d, v->fnorm_b, v->fnorm_sm1, b.fln, st));
-  // head (ISTFTHead.forward), fp32: Linear -> (mag, phase) -> (re, im) -> iDFT frames -> overlap-add
-  VK(gemm(0, EPI_STORE, vg(b.fln, d, v->head, R, b.spec, v->kd), st));
-  VK(vocos_spec(b.spec, R, v->bins, v->kd, st));
-  VK(gemm(0, EPI_STORE, vg(b.spec, v->kd, v->idft, R, b.frames, a.n_fft), st));
-  VK(vocos_ola(b.frames, v->win, B, T, a.n_fft, a.hop_length, audio, st));
-  return 0;
+  tab[B] = (int32_t)R;
+  if (R > B && !audio_packed) return f5h_internal_fail(F5H_EINVAL, "null tensor argument");
+  const size_t need = f5h_vocos_ragged_workspace_size(v, B, R);
+  if (workspace_bytes < need)
+    return f5h_internal_fail(F5H_ENOMEM, "vocos workspace too small: need " + std::to_string(need) + " have " +
+                                             std::to_string(workspace_bytes));
+  VWS ws;
+  VBufs b;
+  ws.base = reinterpret_cast<char*>(workspace);
+  int32_t* off = ws.take<int32_t>(tab.size());
+  vlayout(v, ws, b, 1, (int)R);
+  VHIP(hipSetDevice(v->dev));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  f5h::UseNote used{v->uses, st};
+  // the table travels as kernel arguments: no staging buffer to keep alive, nothing waits, and the caller's
+  // arrays are not read after this call
+  VK(seg_upload(tab.data(), (int64_t)tab.size(), off, st));
+  VK(vocos_im2col_ragged(v->bf, feats, row_stride, frame_stride, chan_stride, off, off + B + 1, B, (int)R,
+                         v->a.input_channels, v->kemb, b.col, st));
+  return vnet(v, b, st, B, 0, off, (int)R, audio_packed);
 }

@@ -101,4 +101,73 @@ hipError_t vocos_ola(const float* frames, const float* win, int B, int T, int n_
   return hipGetLastError();
 }
 
+// ---- Ragged batch (kernels.h): utterance s owns packed rows [off[s], off[s+1]). Padding a batch to equal
+// length is not equivalent: the embed conv and the k7 depthwise convs reach 27 frames across a boundary and
+// LayerNorm of a zero row is not zero, so the kernels below stop every tap at the utterance's own ends.
+
+// vocos_im2col gathering in place from a strided source (the sampler's [B][N][C] output or vocos' [B][C][T]):
+// out[off[s] + t][c*7 + j] = src[s*row_st + (start[s] + t + j - 3)*frame_st + c*chan_st], zero when t + j - 3
+// is outside [0, len_s): the utterance's own zero padding, never a neighbouring frame of the source.
+template <typename TO>
+__global__ void vocos_im2col_ragged_kernel(const float* src, int64_t row_st, int64_t frame_st, int64_t chan_st,
+                                           const int* off, const int* start, int B, int R, int C, int Kp, TO* out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)R * Kp) return;
+  const int col = (int)(i % Kp), row = (int)(i / Kp);
+  float v = 0.f;
+  if (col < C * 7) {
+    const int s = seg_find(off, B, row), base = off[s];
+    const int c = col / 7, j = col - c * 7, q = row - base + j - 3;
+    if (q >= 0 && q < off[s + 1] - base) v = src[s * row_st + (int64_t)(start[s] + q) * frame_st + c * chan_st];
+  }
+  out[i] = from_f32<TO>(v);
+}
+hipError_t vocos_im2col_ragged(int compute, const float* src, int64_t row_st, int64_t frame_st, int64_t chan_st,
+                               const int32_t* off, const int32_t* start, int B, int R, int C, int Kp, void* out,
+                               hipStream_t st) {
+  if (Kp < C * 7 || Kp % 64 || B <= 0 || R <= 0) return hipErrorInvalidValue;
+  const int64_t n = (int64_t)R * Kp;
+  if (compute)
+    hipLaunchKernelGGL(vocos_im2col_ragged_kernel<bf16>, dim3(vblk(n, 256)), dim3(256), 0, st, src, row_st, frame_st,
+                       chan_st, off, start, B, R, C, Kp, (bf16*)out);
+  else
+    hipLaunchKernelGGL(vocos_im2col_ragged_kernel<float>, dim3(vblk(n, 256)), dim3(256), 0, st, src, row_st, frame_st,
+                       chan_st, off, start, B, R, C, Kp, (float*)out);
+  return hipGetLastError();
+}
+
+// vocos_ola per utterance: a thread per (packed row, offset in the hop). Row off[s] + t, t < len_s - 1, gives
+// samples [t*hop, (t+1)*hop) of utterance s, summed over that utterance's frames only, in vocos_ola_kernel's
+// order; the last row of every utterance gives none, so a one-frame utterance contributes nothing. Utterance s
+// starts at sum_{j<s} (len_j - 1)*hop = (off[s] - s)*hop of y.
+__global__ void vocos_ola_ragged_kernel(const float* fr, const float* win, const int* off, int B, int R, int n_fft,
+                                        int hop, float* y) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)R * hop) return;
+  const int row = (int)(i / hop), h = (int)(i - (int64_t)row * hop);
+  const int s = seg_find(off, B, row), base = off[s], T = off[s + 1] - base;
+  if (row - base >= T - 1) return;
+  const int n = (row - base) * hop + h;
+  const int p = n + n_fft / 2;
+  int t0 = p - n_fft + 1 > 0 ? (p - n_fft + 1 + hop - 1) / hop : 0;
+  int t1 = min(p / hop, T - 1);
+  float acc = 0.f, env = 0.f;
+  for (int t = t0; t <= t1; ++t) {
+    const int j = p - t * hop;
+    const float w = win[j];
+    acc += fr[((int64_t)base + t) * n_fft + j];
+    env += w * w;
+  }
+  y[(int64_t)(row - s) * hop + h] = acc / env;
+}
+hipError_t vocos_ola_ragged(const float* frames, const float* win, const int32_t* off, int B, int R, int n_fft,
+                            int hop, float* y, hipStream_t st) {
+  if (B <= 0 || R < B || n_fft % hop) return hipErrorInvalidValue;
+  if (R == B) return hipSuccess;  // every utterance is one frame: no samples
+  const int64_t n = (int64_t)R * hop;
+  hipLaunchKernelGGL(vocos_ola_ragged_kernel, dim3(vblk(n, 256)), dim3(256), 0, st, frames, win, off, B, R, n_fft,
+                     hop, y);
+  return hipGetLastError();
+}
+
 }  // namespace f5h

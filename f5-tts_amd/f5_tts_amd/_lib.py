@@ -74,10 +74,14 @@ EXPORTS = (
     "f5h_vocos_destroy",
     "f5h_vocos_workspace_size",
     "f5h_vocos_decode",
+    "f5h_vocos_ragged_workspace_size",
+    "f5h_vocos_decode_ragged",
     "f5h_mel_create",
     "f5h_mel_destroy",
     "f5h_mel_workspace_size",
     "f5h_mel_forward",
+    "f5h_mel_ragged_workspace_size",
+    "f5h_mel_forward_ragged",
     "f5h_last_error",
     "f5h_version",
 )
@@ -291,6 +295,16 @@ def lib():
     L.f5h_mel_workspace_size.restype = sz
     L.f5h_mel_forward.argtypes = [vp, vp, i32, i32, vp, vp, vp, sz]
     L.f5h_mel_forward.restype = ctypes.c_int
+    if hasattr(L, "f5h_vocos_decode_ragged"):  # absent from an older build (has_ragged)
+        L.f5h_vocos_ragged_workspace_size.argtypes = [vp, i32, i64]
+        L.f5h_vocos_ragged_workspace_size.restype = sz
+        L.f5h_vocos_decode_ragged.argtypes = [vp, vp, i32, vp, i64, i64, i64, ctypes.POINTER(i32), ctypes.POINTER(i32),
+                                              vp, vp, sz]
+        L.f5h_vocos_decode_ragged.restype = ctypes.c_int
+        L.f5h_mel_ragged_workspace_size.argtypes = [vp, i32, i64]
+        L.f5h_mel_ragged_workspace_size.restype = sz
+        L.f5h_mel_forward_ragged.argtypes = [vp, vp, i32, vp, i64, ctypes.POINTER(i32), i32, vp, vp, sz]
+        L.f5h_mel_forward_ragged.restype = ctypes.c_int
     L.f5h_last_error.argtypes = []
     L.f5h_last_error.restype = ctypes.c_char_p
     L.f5h_version.argtypes = []
@@ -316,10 +330,32 @@ def has_mmdit() -> bool:
     return hasattr(lib(), "f5h_op_attention_split")
 
 
+def has_ragged() -> bool:
+    """False for an older build (F5H_LIB) without f5h_vocos_decode_ragged: such a library has no ragged batch
+    entry points (Vocos.decode_ragged, MelSpec.forward_ragged)."""
+    return hasattr(lib(), "f5h_vocos_decode_ragged")
+
+
 def check(rc: int, what: str = "f5h"):
     if rc != 0:
         msg = lib().f5h_last_error().decode(errors="replace")
         raise RuntimeError(f"{what} failed (status {rc}): {msg}")
+
+
+def host_ints(x, n: int, what: str) -> "list[int]":
+    """Python ints of a host-side per-utterance argument (an int for all n, a list/tuple, or a CPU tensor).
+    A device tensor raises: reading it would be a hidden synchronisation, so host values are required."""
+    if torch.is_tensor(x):
+        if x.device.type != "cpu":
+            raise ValueError(f"{what} must be host values (ints, a list or a CPU tensor), not a tensor on {x.device}: "
+                             "reading it back would synchronise the device")
+        x = x.reshape(-1).tolist()
+    elif isinstance(x, int):
+        x = [x] * n
+    vals = [int(v) for v in x]
+    if len(vals) != n:
+        raise ValueError(f"{what} has {len(vals)} entries for {n} utterances")
+    return vals
 
 
 def ptr(t) -> int | None:

@@ -346,3 +346,57 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
         yield cross_fade(waves, cross_fade_duration), target_sample_rate, np.concatenate(specs, axis=1)
     else:
         yield None, target_sample_rate, None
+
+
+def infer_batch(items, model_obj, vocoder, *, nfe_step=nfe_step, cfg_strength=cfg_strength,
+                sway_sampling_coef=sway_sampling_coef, speed=1.0, seed=None, target_rms=target_rms, max_batch=32):
+    """Batch synthesis to waveforms, the reference's eval recipe (eval/utils_eval.py:109-148 and
+    eval/eval_infer_batch.py:188-212) on ragged batches. `items`: `(ref_audio, ref_text, gen_text)` per utterance,
+    `ref_audio` a WAV path or an `(audio [C, n] tensor, sr)` tuple as in `infer_process`. Per item: mono, RMS boost
+    to `target_rms` when quieter, resample to 24 kHz; a space after a `ref_text` ending in a single-byte character;
+    total frames = ref + int(ref / len(ref_text bytes) * len(gen_text bytes) / speed) with ref the prompt's mel
+    frames. The items are grouped into length buckets of at most `max_batch` (`parallel.bucket`); each bucket is one
+    `model_obj.mel_spec.forward_ragged`, one `model_obj.sample(cond, text, duration, lens=...)` with host lengths and
+    one `vocoder.decode_ragged(out, ref, total - ref)`; the RMS boost is undone only where it was applied.
+    Returns `[(wave, 24000)]` in input order, `wave` a 1-D float32 numpy array of (total - ref - 1) * 256 samples."""
+    from . import parallel
+
+    device = getattr(model_obj, "device", None) or _default_device()
+    prep = []
+    for k, (ref_audio, ref_text, gen_text) in enumerate(items):
+        audio, sr = load_audio(ref_audio) if isinstance(ref_audio, str) else ref_audio
+        if audio.ndim == 1:
+            audio = audio[None]
+        if audio.shape[0] > 1:
+            audio = torch.mean(audio, dim=0, keepdim=True)
+        rms = torch.sqrt(torch.mean(torch.square(audio)))
+        if rms < target_rms:
+            audio = audio * target_rms / rms
+        if sr != target_sample_rate:
+            audio = resample(audio, sr, target_sample_rate)
+        if len(ref_text[-1].encode("utf-8")) == 1:
+            ref_text = ref_text + " "
+        ref = 1 + audio.shape[-1] // hop_length  # the prompt's mel frames (torch.stft center=True)
+        total = ref + int(ref / len(ref_text.encode("utf-8")) * len(gen_text.encode("utf-8")) / speed)
+        if total <= ref:
+            raise ValueError(f"item {k}: nothing to generate ({len(gen_text.encode('utf-8'))} bytes of gen_text)")
+        prep.append(dict(audio=audio[0], rms=rms, text=convert_char_to_pinyin([ref_text + gen_text])[0], ref=ref,
+                         total=total))
+    waves = [None] * len(prep)
+    with torch.inference_mode():
+        for b in parallel.bucket(range(len(prep)), [p["total"] for p in prep], max_batch):
+            cond, frames = model_obj.mel_spec.forward_ragged([prep[i]["audio"].to(device) for i in b])
+            assert frames == [prep[i]["ref"] for i in b]
+            ref = [prep[i]["ref"] for i in b]
+            total = [prep[i]["total"] for i in b]
+            # lengths stay host tensors: CFM.sample evaluates its duration rule on the host without a sync
+            generated, _ = model_obj.sample(cond=cond, text=[prep[i]["text"] for i in b],
+                                            duration=torch.tensor(total, dtype=torch.long),
+                                            lens=torch.tensor(ref, dtype=torch.long), steps=nfe_step,
+                                            cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed)
+            del _
+            for i, wav in zip(b, vocoder.decode_ragged(generated, ref, [t - r for t, r in zip(total, ref)])):
+                if prep[i]["rms"] < target_rms:
+                    wav = wav * prep[i]["rms"] / target_rms
+                waves[i] = wav
+    return [(w.cpu().numpy(), target_sample_rate) for w in waves]

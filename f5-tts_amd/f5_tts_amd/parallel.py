@@ -117,9 +117,11 @@ def plan(totals, world: int, max_batch: int):
 
 
 def run_sharded(utts, sample_fn, *, rank: int, world: int, max_batch: int = 32, device=None, group=None,
-                plan_all=None):
+                plan_all=None, vocoder=None):
     """Run a whole utterance job data-parallel and return {index: generated mel [total-ref, C]} on
-    every rank.
+    every rank; with a `vocoder` (the HIP `Vocos`, or any object with `decode_ragged` and `hop_length`), each
+    batch is decoded ragged straight from the sampler's output and the dict holds the waves instead,
+    {index: wave [(total-ref-1) * hop]}, which then are what the gather carries.
 
     utts: list of dicts with `cond` [ref_i(, padded), C] mel, `text` (str list or id list), `ref` (prompt
     frames) and `total` (total frames), the fields of one prompt in eval_infer_batch.py:182-185.
@@ -141,10 +143,21 @@ def run_sharded(utts, sample_fn, *, rank: int, world: int, max_batch: int = 32, 
         dur = torch.tensor([utts[i]["total"] for i in b], dtype=torch.long)
         lens = torch.tensor([utts[i]["ref"] for i in b], dtype=torch.long)
         out = sample_fn(cond, text, dur, lens)
+        if vocoder is not None:
+            waves = vocoder.decode_ragged(out, lens, dur - lens)
+            local.update(zip(b, waves))
+            continue
         for j, i in enumerate(b):
             local[i] = out[j, utts[i]["ref"]: utts[i]["total"]]
     if world == 1:
         return local
+    if vocoder is not None:  # the waves travel as one-channel "mels" of their planned lengths
+        hop = vocoder.hop_length
+        layout = [[(i, (utts[i]["total"] - utts[i]["ref"] - 1) * hop) for b in plan_all[r] for i in b]
+                  for r in range(world)]
+        got = gather_mels({i: w[:, None] for i, w in local.items()}, device=device, group=group, layout=layout,
+                          num_channels=1)
+        return {i: w[:, 0] for i, w in got.items()}
     layout = [[(i, utts[i]["total"] - utts[i]["ref"]) for b in plan_all[r] for i in b] for r in range(world)]
     return gather_mels(local, device=device, group=group, layout=layout, num_channels=utts[0]["cond"].shape[-1])
 

@@ -7,7 +7,9 @@ checkpoint). This class keeps that surface: construct, `load_state_dict(state_di
 parameter names (feature-extractor buffers are ignored, as they are not on the decode path),
 `.to(device)` / `.eval()`, and `decode(features_input)` mapping mel [B, 100, T] fp32 to audio
 [B, (T - 1) * 256] (torch.istft center=True length). The work runs in libf5h.so
-(`f5h_vocos_decode`, include/f5h.h); there is no PyTorch fallback.
+(`f5h_vocos_decode`, include/f5h.h); there is no PyTorch fallback. `decode_ragged` is the batch form for
+utterances of unequal length (`f5h_vocos_decode_ragged`): it reads each utterance's frames in place from the
+sampler's output and returns one wave per utterance, bitwise equal to `decode` of that utterance alone.
 """
 
 from __future__ import annotations
@@ -127,6 +129,62 @@ class Vocos:
         return audio
 
     __call__ = decode
+
+    @property
+    def hop_length(self) -> int:
+        return self.arch["hop_length"]
+
+    def decode_ragged(self, feats: torch.Tensor, starts, lens, channels_last: bool = True) -> "list[torch.Tensor]":
+        """A batch of utterances of unequal length in one pass (`f5h_vocos_decode_ragged`): utterance i is frames
+        [starts[i], starts[i] + lens[i]) of row i of `feats`, which is the sampler's [B, N, C] output
+        (`channels_last`) or vocos' [B, C, T] layout, read in place through its strides. Returns B 1-D fp32
+        waves of (lens[i] - 1) * hop samples (empty for one frame), views into one packed buffer, each equal bit
+        for bit to `decode` of that utterance alone. `starts` / `lens` are host values (an int for all, a list
+        or a CPU tensor): a device tensor raises ValueError, so there is no hidden synchronisation."""
+        if feats.dim() == 2:
+            feats = feats[None]
+        if feats.dim() != 3:
+            raise ValueError(f"feats must be [B, N, C] (or [B, C, T] with channels_last=False), got {tuple(feats.shape)}")
+        B, N, C = feats.shape if channels_last else (feats.shape[0], feats.shape[2], feats.shape[1])
+        if C != self.arch["input_channels"]:
+            raise ValueError(f"expected {self.arch['input_channels']} mel channels, got {C}")
+        if B < 1:
+            raise ValueError("decode_ragged needs at least one utterance")
+        starts = _lib.host_ints(starts, B, "starts")
+        lens = _lib.host_ints(lens, B, "lens")
+        for i, (s0, n) in enumerate(zip(starts, lens)):
+            if n < 1:
+                raise ValueError(f"utterance {i}: length {n} (at least one frame)")
+            if s0 < 0 or s0 + n > N:
+                raise ValueError(f"utterance {i}: frames [{s0}, {s0 + n}) are outside the {N} frames of feats")
+        total = sum(lens)
+        if total > 1 << 24:
+            raise ValueError(f"{total} frames in all: at most 2^24 per call")
+        L = _lib.lib()
+        if not _lib.has_ragged():
+            raise RuntimeError("this libf5h.so has no ragged batch entry points (f5h_vocos_decode_ragged)")
+        h = self._engine()
+        feats = feats.to(self.device, torch.float32)
+        row_st, frame_st, chan_st = feats.stride() if channels_last else (feats.stride(0), feats.stride(2), feats.stride(1))
+        hop = self.arch["hop_length"]
+        audio = torch.empty((total - B) * hop, dtype=torch.float32, device=self.device)
+        i32 = ctypes.c_int32 * B
+        need = int(L.f5h_vocos_ragged_workspace_size(h, B, total))
+        stream = _lib.stream_handle(self.device)
+        with self._lock:
+            ws = self._ws.get((stream, need))
+            if ws is None:
+                ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+                self._ws = {(stream, need): ws}
+            with torch.cuda.device(self.device):
+                _lib.check(L.f5h_vocos_decode_ragged(h, stream, B, feats.data_ptr(), row_st, frame_st, chan_st,
+                                                     i32(*starts), i32(*lens), audio.data_ptr(), ws.data_ptr(),
+                                                     ws.numel()), "f5h_vocos_decode_ragged")
+        out, o = [], 0
+        for n in lens:
+            out.append(audio[o: o + (n - 1) * hop])
+            o += (n - 1) * hop
+        return out
 
 
 def param_shapes(arch: dict = VOCOS_MEL_24KHZ) -> "dict[str, tuple]":

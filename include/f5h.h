@@ -511,6 +511,21 @@ size_t f5h_vocos_workspace_size(const f5h_vocos* v, int32_t B, int32_t T);
  * (torch.istft center=True length). Device pointers; work enqueued on `stream`. */
 int f5h_vocos_decode(f5h_vocos* v, void* stream, int32_t B, int32_t T, const float* mel, float* audio,
                      void* workspace, size_t workspace_bytes);
+/* A batch of B utterances of unequal length in one pass (the eval driver's per-utterance
+ * `gen[ref_len:total_len]` -> `vocoder.decode`, eval/eval_infer_batch.py:202-212). Utterance i is frames
+ * [starts[i], starts[i] + lens[i]) of row i of `feats`, read in place through element strides:
+ * feats[i*row_stride + t*frame_stride + c*chan_stride], so both the sampler's [B][N][C] output and vocos'
+ * [B][C][T] layout are sources without a slice, permute or copy. The utterances run as packed rows with no padding
+ * rows; the convolutions and the overlap-add stop at each utterance's own ends, so every wave equals
+ * f5h_vocos_decode of that utterance alone bit for bit (zero-padding to one length does not: the convolutions
+ * reach 27 frames across a boundary). audio_packed: utterance i at sum_{j<i} (lens[j] - 1)*hop, (lens[i] - 1)*hop
+ * samples (none for lens[i] = 1). starts / lens are HOST arrays, consumed before the call returns (the caller may
+ * free or overwrite them at once); the call does not synchronise the device or the stream. F5H_EINVAL names the
+ * offending row for lens[i] < 1, starts[i] < 0 and a total above 2^24 frames. */
+size_t f5h_vocos_ragged_workspace_size(const f5h_vocos* v, int32_t B, int64_t total_frames);
+int f5h_vocos_decode_ragged(f5h_vocos* v, void* stream, int32_t B, const float* feats, int64_t row_stride,
+                            int64_t frame_stride, int64_t chan_stride, const int32_t* starts, const int32_t* lens,
+                            float* audio_packed, void* workspace, size_t workspace_bytes);
 
 /* ---------------------------------------------------------------------------------------
  * Log-mel front end (wav -> mel), SURVEY §8(f2): replaces get_vocos_mel_spectrogram
@@ -532,6 +547,15 @@ size_t f5h_mel_workspace_size(const f5h_mel* m, int32_t B, int32_t L);
 /* wav [B][L] fp32 -> mel [B][n_mels][T] fp32 (device pointers, enqueued on `stream`) */
 int f5h_mel_forward(f5h_mel* m, void* stream, int32_t B, int32_t L, const float* wav, float* mel, void* workspace,
                     size_t workspace_bytes);
+/* B waves of unequal length in one pass (the eval driver computes each prompt's log-mel separately and pads
+ * the mels, eval/utils_eval.py:58-66,130). Wave i is wav[i*wav_stride .. + lens[i]) and gives T_i = 1 + lens[i]/hop
+ * frames, reflected at its own end; cond [B][T_out][n_mels] (frame-major, the layout CFM.sample takes) holds them
+ * with exact zeros for frames >= T_i, i.e. the zero-padded batch of the per-wave log-mels, bit for bit.
+ * total_frames = sum T_i. lens is a HOST array, consumed before the call returns; no synchronisation.
+ * F5H_EINVAL names the offending wave for lens[i] <= n_fft/2, T_i > T_out and a total above 2^24 frames. */
+size_t f5h_mel_ragged_workspace_size(const f5h_mel* m, int32_t B, int64_t total_frames);
+int f5h_mel_forward_ragged(f5h_mel* m, void* stream, int32_t B, const float* wav, int64_t wav_stride,
+                           const int32_t* lens, int32_t T_out, float* cond, void* workspace, size_t workspace_bytes);
 
 const char* f5h_last_error(void);
 const char* f5h_version(void);
