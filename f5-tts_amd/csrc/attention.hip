@@ -79,7 +79,11 @@ F5H_DEV void attn_block(int& qb, int& bh) {
 // WT: the store policy's write-through form of the O store (AttnArgs::store_wt; a separately compiled kernel, so
 // neither form carries a switch): each wave transposes its 32 x 64 O tile through LDS so that every store
 // instruction writes whole 128-B rows (8 lanes x 16 B), through a buffer descriptor with the sc1 policy.
-template <typename T, bool PRESCALED, int NW, bool RSM, bool WT = false>
+// RG: two key ranges (AttnArgs::kv_len2; a separately compiled kernel as well). Tile index kt counts the first
+// range's tiles [0, nt1), rows kt * 64 up to klen, then the second range's, rows start2 + (kt - nt1) * 64 up to
+// end2: the ring, the waits and the running max see one sequence of ntile tiles. A tile's DMA extent ends at its
+// range's end (not at L), so rows between the ranges read as zero and are never loaded.
+template <typename T, bool PRESCALED, int NW, bool RSM, bool WT = false, bool RG = false>
 __global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
   typedef Op16<T> OP;
   typedef typename OP::v8 v8;
@@ -110,7 +114,20 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
   const T* V = reinterpret_cast<const T*>(a.v) + base;
   int klen = L;
   if (a.kv_len) klen = min(klen, a.kv_len[s_idx]);
-  const int ntile = (klen + 63) / 64;
+  int nt1 = 0, start2 = 0, end2 = 0;  // RG only
+  if constexpr (RG) {
+    start2 = __builtin_amdgcn_readfirstlane(max(0, min(a.kv_start2, L)));
+    klen = __builtin_amdgcn_readfirstlane(max(0, min(klen, start2)));
+    end2 = __builtin_amdgcn_readfirstlane(start2 + max(0, min(a.kv_len2[s_idx], L - start2)));
+    nt1 = (klen + 63) / 64;
+  }
+  const int ntile = RG ? nt1 + (end2 - start2 + 63) / 64 : (klen + 63) / 64;
+  // RG: first key row and range end of tile kt (tiles past ntile: an empty span)
+  auto tile_span = [&](const int kt, int& kb, int& kend) __attribute__((always_inline)) {
+    const bool second = kt >= nt1;
+    kb = second ? start2 + (kt - nt1) * 64 : kt * 64;
+    kend = second ? end2 : klen;
+  };
 
   const int qrow = qb * (32 * NW) + wid * 32 + (lane & 31);
 
@@ -134,10 +151,20 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
     uint4* Vs = Ks + 512;
     // wave-uniform by construction; readfirstlane makes it provably so (else the descriptor sits in VGPRs and
     // hipcc wraps every DMA piece in a waterfall loop, cdna_hip_programming.md T20)
-    const int rows = live ? min(64, L - kt * 64) : max(0, min(64, L - kt * 64));
+    int rows;
+    int64_t koff;  // the tile's first key, in elements
+    if constexpr (RG) {  // the tile's own base row and range end
+      int kb, kend;
+      tile_span(kt, kb, kend);
+      rows = live ? min(64, kend - kb) : max(0, min(64, kend - kb));
+      koff = (int64_t)__builtin_amdgcn_readfirstlane(kb) * 64;
+    } else {
+      rows = live ? min(64, L - kt * 64) : max(0, min(64, L - kt * 64));
+      koff = (int64_t)kt * 4096;
+    }
     const uint32_t ext = (uint32_t)__builtin_amdgcn_readfirstlane(rows * 128);
-    const __amdgpu_buffer_rsrc_t krs = rsrc_of(K + (int64_t)kt * 4096, ext);
-    const __amdgpu_buffer_rsrc_t vrs = rsrc_of(V + (int64_t)kt * 4096, ext);
+    const __amdgpu_buffer_rsrc_t krs = rsrc_of(K + koff, ext);
+    const __amdgpu_buffer_rsrc_t vrs = rsrc_of(V + koff, ext);
 #pragma unroll
     for (int r = 0; r < CPW; ++r) {
       dma16(krs, (LDS_PTR(void))(Ks + (r * NW + wid_s) * 64), dvoff[r], 0);
@@ -204,7 +231,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
   for (int ks = 0; ks < 4; ++ks) {
     qf[ks] = __builtin_bit_cast(v8, qv[ks]);
     if constexpr (!PRESCALED) {  // scores in log2 units: fold scale*log2(e) into q
-      const float c = a.scale * 1.4426950408889634f;
+      const float c = kAttnScale * 1.4426950408889634f;
 #pragma unroll
       for (int j = 0; j < 8; ++j) qf[ks][j] = from_f32<T>(to_f32(qf[ks][j]) * c);
     }
@@ -263,13 +290,15 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
 #pragma unroll
       for (int ks = 1; ks < 4; ++ks) sacc[t] = OP::mma32(__builtin_bit_cast(v8, kf[t][ks]), qf[ks], sacc[t]);
     }
-    if (kt * 64 + 64 > klen) {  // ragged last tile: keys past klen get p = 0
-      const int kbase = kt * 64 + 4 * h;
+    int kb = kt * 64, kend = klen;
+    if constexpr (RG) tile_span(kt, kb, kend);
+    if (kb + 64 > kend) {  // ragged last tile (of its range): keys past the end get p = 0
+      const int kbase = kb + 4 * h;
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          if (kbase + t * 32 + (r & 3) + 8 * (r >> 2) >= klen) sacc[t][r] = -INFINITY;
+          if (kbase + t * 32 + (r & 3) + 8 * (r >> 2) >= kend) sacc[t][r] = -INFINITY;
     }
     if constexpr (FIRST || SAFE) {
       float mx = -INFINITY;
@@ -532,6 +561,8 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
 }
 
 // ---------------------------------------------------------------- fp32 parity kernel
+// RG: two key ranges (AttnArgs::kv_len2), walked one after the other in 32-key tiles by the same loop body
+template <bool RG>
 __global__ __launch_bounds__(64) void attn_f32_kernel(AttnArgs a) {
   const ProbeT probe_t = probe_enter(a.probe);
   __shared__ float Ks[32][65];
@@ -558,7 +589,16 @@ __global__ __launch_bounds__(64) void attn_f32_kernel(AttnArgs a) {
     o[d] = 0.f;
   }
   float m_run = -INFINITY, l_run = 0.f;
-  for (int k0 = 0; k0 < klen; k0 += 32) {
+  int start2 = 0, end2 = 0;
+  if constexpr (RG) {
+    start2 = max(0, min(a.kv_start2, L));
+    end2 = start2 + max(0, min(a.kv_len2[s_idx], L - start2));
+    klen = max(0, min(klen, start2));
+  }
+  const int klen1 = klen;
+  for (int rg = 0; rg < (RG ? 2 : 1); ++rg)
+  for (int k0 = rg ? start2 : 0; k0 < (rg ? end2 : klen1); k0 += 32) {
+    if constexpr (RG) klen = rg ? end2 : klen1;  // the range's end: rows past it are not read
     __syncthreads();
     for (int i = lane; i < 32 * 64; i += 64) {
       int r = i >> 6, d = i & 63, key = k0 + r;
@@ -573,7 +613,7 @@ __global__ __launch_bounds__(64) void attn_f32_kernel(AttnArgs a) {
       float acc = 0.f;
 #pragma unroll
       for (int d = 0; d < 64; ++d) acc = fmaf(q[d], Ks[r][d], acc);
-      sc[r] = (k0 + r < klen) ? (a.prescaled ? acc : acc * a.scale) : -INFINITY;
+      sc[r] = (k0 + r < klen) ? (a.prescaled ? acc : acc * kAttnScale) : -INFINITY;
       mx = fmaxf(mx, sc[r]);
     }
     const float alpha = a.prescaled ? exp2f(m_run - mx) : expf(m_run - mx);
@@ -593,7 +633,7 @@ __global__ __launch_bounds__(64) void attn_f32_kernel(AttnArgs a) {
     const int sp = a.o_split > 0 ? a.o_split : L;  // split output (AttnArgs::o_split)
     float* O = qrow < sp ? reinterpret_cast<float*>(a.o) + (((int64_t)s_idx * sp + qrow) * a.H + head) * 64
                          : reinterpret_cast<float*>(a.o2) + (((int64_t)s_idx * (L - sp) + (qrow - sp)) * a.H + head) * 64;
-    const float inv = 1.f / l_run;
+    const float inv = (RG && !(l_run > 0.f)) ? 0.f : 1.f / l_run;  // RG: both ranges empty -> 0
 #pragma unroll
     for (int d = 0; d < 64; ++d) O[d] = o[d] * inv;
   }
@@ -611,6 +651,15 @@ static void launch16(const AttnArgs& a, hipStream_t st) {
     const char* v = getenv("F5H_ATTN_ROWSUM");
     return v && !strcmp(v, "mfma");
   }();
+  if (a.kv_len2) {  // two key ranges: kernels of their own (VALU row sums; the engine's form with its store policy)
+    if (a.prescaled && a.store_wt && attn_wt_ok(a))
+      hipLaunchKernelGGL((attn16_kernel<T, true, NW, false, true, true>), grid, dim3(64 * NW), 0, st, a);
+    else if (a.prescaled)
+      hipLaunchKernelGGL((attn16_kernel<T, true, NW, false, false, true>), grid, dim3(64 * NW), 0, st, a);
+    else
+      hipLaunchKernelGGL((attn16_kernel<T, false, NW, false, false, true>), grid, dim3(64 * NW), 0, st, a);
+    return;
+  }
   // Store policy: the engine's form (prescaled q, VALU row sums) has a write-through variant
   if (a.prescaled && !rsm && a.store_wt && attn_wt_ok(a)) {
     hipLaunchKernelGGL((attn16_kernel<T, true, NW, false, true>), grid, dim3(64 * NW), 0, st, a);
@@ -648,7 +697,10 @@ hipError_t attention(int compute, const AttnArgs& a0, hipStream_t st) {
     case F5H_C_FP16: launch16<f16>(a, st); break;
     default: {
       dim3 grid((a.L + 63) / 64, a.S * a.H);
-      hipLaunchKernelGGL(attn_f32_kernel, grid, dim3(64), 0, st, a);
+      if (a.kv_len2)
+        hipLaunchKernelGGL(attn_f32_kernel<true>, grid, dim3(64), 0, st, a);
+      else
+        hipLaunchKernelGGL(attn_f32_kernel<false>, grid, dim3(64), 0, st, a);
     }
   }
   return hipGetLastError();

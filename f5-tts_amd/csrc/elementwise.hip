@@ -616,16 +616,20 @@ F5H_DEV void dwconv_ln_row(const float* x, int64_t base, int n, int L, int C, co
 }
 template <typename TO>
 __global__ void dwconv_ln_kernel(const float* x, int S, int L, int C, const float* w, const float* bias,
-                                 const float* lw, const float* lb, TO* out) {
+                                 const float* lw, const float* lb, TO* out, const int* len, int len_mod) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= S * L) return;
   const int s = row / L, n = row - s * L;
-  dwconv_ln_row<TO>(x, (int64_t)s * L, n, L, C, w, bias, lw, lb, out, lane);
+  // len: the sequence ends at row min(L, len[s % len_mod]); taps past it are zero, as taps past L (rows past it are
+  // still written, from whatever they hold: their consumers mask them)
+  const int Ls = len ? max(0, min(L, len[s % len_mod])) : L;
+  dwconv_ln_row<TO>(x, (int64_t)s * L, n, Ls, C, w, bias, lw, lb, out, lane);
 }
 hipError_t dwconv_ln(int compute, const float* x, int S, int L, int C, const float* dw_w, const float* dw_b,
-                     const float* ln_w, const float* ln_b, void* out, hipStream_t st) {
-  if (C > 1024) return hipErrorInvalidValue;
-  F5H_OP_DISPATCH(compute, T, hipLaunchKernelGGL(dwconv_ln_kernel<T>, dim3(nblk(S * L, 4)), dim3(256), 0, st, x, S, L, C, dw_w, dw_b, ln_w, ln_b, (T*)out););
+                     const float* ln_w, const float* ln_b, void* out, hipStream_t st, const int32_t* len,
+                     int len_mod) {
+  if (C > 1024 || (len && len_mod <= 0)) return hipErrorInvalidValue;
+  F5H_OP_DISPATCH(compute, T, hipLaunchKernelGGL(dwconv_ln_kernel<T>, dim3(nblk(S * L, 4)), dim3(256), 0, st, x, S, L, C, dw_w, dw_b, ln_w, ln_b, (T*)out, len, len_mod););
   return hipGetLastError();
 }
 // The same over packed rows of unequal sequences (kernels.h, ragged batches): the row's sequence comes from the
@@ -649,10 +653,13 @@ hipError_t dwconv_ln_ragged(int compute, const float* x, const int32_t* off, int
 // out = gamma * (x * Nx) + beta + x
 // Deterministic two-stage column reduction: partial[z][s][c] over 64-row chunks, then a
 // fixed-order sum (no float atomics: results must not depend on arrival order).
-__global__ void grn_sumsq_kernel(const float* x, int S, int L, int C, float* partial) {
+// len: only rows below min(L, len[s % len_mod]) count; the partials of chunks past it are exact zeros, so the sum over
+// the chunks has the bits of the sequence alone at that length
+__global__ void grn_sumsq_kernel(const float* x, int S, int L, int C, float* partial, const int* len, int len_mod) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x, s = blockIdx.y, z = blockIdx.z;
   if (c >= C) return;
-  const int n0 = z * 64, n1 = min(L, n0 + 64);
+  const int Ls = len ? min(L, len[s % len_mod]) : L;
+  const int n0 = z * 64, n1 = min(Ls, n0 + 64);
   float acc = 0.f;
   for (int n = n0; n < n1; ++n) {
     float v = x[((int64_t)s * L + n) * C + c];
@@ -695,11 +702,12 @@ __global__ void grn_apply_kernel(const float* x, int L, int C, const float* nx, 
   out[i] = from_f32<TO>(gamma[c] * (v * nx[(int64_t)s * C + c]) + beta[c] + v);
 }
 hipError_t grn(int compute, const float* x, int S, int L, int C, const float* gamma, const float* beta,
-               float* scratch, void* out, hipStream_t st) {
+               float* scratch, void* out, hipStream_t st, const int32_t* len, int len_mod) {
+  if (len && len_mod <= 0) return hipErrorInvalidValue;
   // scratch: [nz*S*C] partials then [S*C] normalisers
   const int nz = (int)nblk(L, 64);
   float* nx = scratch + (size_t)nz * S * C;
-  hipLaunchKernelGGL(grn_sumsq_kernel, dim3(nblk(C, 256), S, nz), dim3(256), 0, st, x, S, L, C, scratch);
+  hipLaunchKernelGGL(grn_sumsq_kernel, dim3(nblk(C, 256), S, nz), dim3(256), 0, st, x, S, L, C, scratch, len, len_mod);
   hipLaunchKernelGGL(grn_norm_kernel, dim3(S), dim3(1024), 0, st, scratch, nz, S, C, nx);
   scratch = nx;
   const int64_t total = (int64_t)S * L * C;
@@ -965,6 +973,21 @@ __global__ void kvlen_kernel(const int32_t* dur, int B, int S, int off, int32_t*
 }
 hipError_t build_kvlen(const int32_t* dur, int B, int S, int off, int32_t* kv, hipStream_t st) {
   hipLaunchKernelGGL(kvlen_kernel, dim3(nblk(S, 64)), dim3(64), 0, st, dur, B, S, off, kv);
+  return hipGetLastError();
+}
+// One wave per sequence: the highest non-filler position, by a wave max over strided positions
+__global__ void textlen_kernel(const int64_t* text, int B, int S, int nt, int32_t* len) {
+  const int s = blockIdx.x, lane = threadIdx.x;
+  const int64_t* t = text + (int64_t)(s % B) * nt;
+  int last = 0;
+  for (int j = lane; j < nt; j += 64)
+    if (t[j] != -1) last = j + 1;
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) last = max(last, __shfl_xor(last, m));
+  if (lane == 0) len[s] = last;
+}
+hipError_t build_textlen(const int64_t* text, int B, int S, int nt, int32_t* len, hipStream_t st) {
+  hipLaunchKernelGGL(textlen_kernel, dim3(S), dim3(64), 0, st, text, B, S, nt, len);
   return hipGetLastError();
 }
 

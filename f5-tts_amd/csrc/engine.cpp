@@ -655,6 +655,12 @@ struct Bufs {
   // MMDiT text stream (null otherwise), see layout
   void *c0, *ch, *caop, *co, *cf;
   uint8_t* ckeep;
+  // isolation (use_batch_mask == 2): the text key range's length per sequence (MMDiT, AttnArgs::kv_len2); UNetT's row
+  // mask over the N audio rows of a sequence (b.rowkeep counts the time token's row). The latter lives in keepfill,
+  // which only the ConvNeXt text blocks read and UNetT has none of (written after the text embedding; a UNetT with
+  // text blocks would get a buffer of its own), so UNetT's workspace keeps its size
+  int32_t* tlen;
+  uint8_t* rowkeep_n;
   // UNetT residual stream (operand dtype): xs[0..depth/2] -- layer l < depth/2 reads xs[l] (its
   // skip connection, kept) and writes xs[l+1]; later layers ping-pong between pp[0] and pp[1]
   std::vector<void*> xs;
@@ -746,6 +752,8 @@ static void layout(const f5h_engine* e, WS& ws, Bufs& b, int B, int N, int nfe, 
   b.co = mm ? ws.take<char>(crows * inner * es) : nullptr;
   b.cf = mm ? ws.take<char>(crows * a.ff_dim * es) : nullptr;
   b.ckeep = mm ? ws.take<uint8_t>(crows) : nullptr;
+  b.tlen = mm ? ws.take<int32_t>(S) : nullptr;
+  b.rowkeep_n = a.backbone != F5H_UNETT ? nullptr : a.conv_layers > 0 ? ws.take<uint8_t>((size_t)S * N) : b.keepfill;
 }
 
 // ---------------------------------------------------------------- probe
@@ -795,6 +803,10 @@ struct Ctx {
   hipStream_t st;
   Bufs b;
   int B, N, nt, S, L, nfe, use_cfg, batch_mask;
+  // use_batch_mask == 2 (batch_mask is 1 as well): every sequence is computed as if it were alone -- pad rows and
+  // pad keys of the batch reach no valid row (conv_pos row masks on every backbone, key lengths on every attention,
+  // the text embedding's GRN and depthwise conv bounded by the sequence's own length)
+  int isolate;
   int method, steps;  // f5h_ode_method and grid steps of an f5h_sample_ode call; nfe = steps x stages evaluations
   int drop_audio, drop_text;  // single-branch forward only (f5h_forward with cfg_infer = 0)
   hipStream_t st2;            // second stream for the unconditional branch (step-graph capture), or null
@@ -847,6 +859,8 @@ static int prologue(Ctx& c, const float* t_host, int nt_vals, const float* cond,
   if (c.batch_mask) {
     KCK(build_rowkeep(duration, c.B, c.S, c.L, off, b.rowkeep, st));
     KCK(build_kvlen(duration, c.B, c.S, off, b.kvlen, st));
+    // MMDiT isolated: the text keys' range, from the text as given (before drop_text, as c_mask)
+    if (mm && c.isolate) KCK(build_textlen(text, c.B, c.S, c.nt, b.tlen, st));
   }
   // ---- time embedding for every grid point used, then the AdaLN table
   {
@@ -914,12 +928,15 @@ static int prologue(Ctx& c, const float* t_host, int nt_vals, const float* cond,
     t.keep = b.keepfill;
     KCK(text_embed(t, st));
     const int S2 = 2 * c.B, R2 = S2 * c.N;
+    // isolation: the depthwise conv's taps and GRN's norm over time stop at the sequence's own length (the reference
+    // runs both over the padded axis, modules.py:236-245, 260-264)
+    const int32_t* tl = c.isolate ? duration : nullptr;
     for (int i = 0; i < a.conv_layers; ++i) {
       CNX& x = e->cnx[i];
-      KCK(dwconv_ln(bf, b.te, S2, c.N, td, x.dw_w, x.dw_b, x.ln_w, x.ln_b, b.dwln, st));
+      KCK(dwconv_ln(bf, b.te, S2, c.N, td, x.dw_w, x.dw_b, x.ln_w, x.ln_b, b.dwln, st, tl, c.B));
       GemmArgs g = gargs(b.dwln, td, x.pw1, R2, b.pw1o, 2 * td);
       KCK(gemm(bf, EPI_GELU_ERF, g, st));
-      KCK(grn(bf, b.pw1o, S2, c.N, 2 * td, x.gamma, x.beta, b.grn_scr, b.grno, st));
+      KCK(grn(bf, b.pw1o, S2, c.N, 2 * td, x.gamma, x.beta, b.grn_scr, b.grno, st, tl, c.B));
       g = gargs(b.grno, 2 * td, x.pw2, R2, b.te, td);
       g.rowkeep = a.text_mask_padding ? b.keepfill : nullptr;
       KCK(gemm(bf, EPI_RESID_FILL, g, st));
@@ -940,6 +957,8 @@ static int prologue(Ctx& c, const float* t_host, int nt_vals, const float* cond,
       KCK(text_upsample(u, st));
     }
   }
+  // UNetT isolated: the audio rows' mask (after the text embedding, whose keepfill bytes it may take over)
+  if (c.isolate && b.rowkeep_n) KCK(build_rowkeep(duration, c.B, c.S, c.N, 0, b.rowkeep_n, st));
   // ---- hoisted input projection: P = [step_cond | text] . W_ct^T + b
   const float* te = a.text_average_upsampling ? b.te_up : b.te;
   // (MMDiT: no text columns, the audio embedding sees cat(x, cond) only)
@@ -1018,7 +1037,8 @@ static int backbone_part(Ctx& c, int s0, int ns, hipStream_t st) {
     cv.S = ns;
     cv.L = c.N;
     cv.d = d;
-    cv.rowkeep = dit ? keep : nullptr;  // UNetT's InputEmbedding passes no mask (unett.py:100)
+    // UNetT's InputEmbedding passes no mask (unett.py:100); isolated, its N audio rows are masked as DiT's are
+    cv.rowkeep = dit ? keep : (c.isolate ? b.rowkeep_n + no : nullptr);
     cv.x = b.h0 + no * d;
     cv.x_f32 = 1;
     cv.w = e->conv_w[0];
@@ -1182,10 +1202,9 @@ static int backbone_part(Ctx& c, int s0, int ns, hipStream_t st) {
       at.S = ns;
       at.H = H;
       at.L = c.L;
-      at.kv_len = (a.attn_mask_enabled && c.batch_mask) ? b.kvlen + s0 : nullptr;
+      at.kv_len = ((a.attn_mask_enabled || c.isolate) && c.batch_mask) ? b.kvlen + s0 : nullptr;
       // pad query rows' outputs are zeroed after to_out (modules.py:551-553): their blocks are skipped
       at.q_len = (c.batch_mask && e->pad_skip) ? b.kvlen + s0 : nullptr;
-      at.scale = 0.125f;
       at.prescaled = 1;
       at.store_wt = attention_store_wt(bf, at, store_want(c.store, KC_ATTN));
       count_store(at.store_wt);
@@ -1302,7 +1321,8 @@ static int backbone_part(Ctx& c, int s0, int ns, hipStream_t st) {
 // output split back (AttnArgs::o_split), then per stream the out-projection, LN-modulate, FFN1 and FFN2 with the
 // kernels the DiT block uses. The last block (context_pre_only) only pre-normalises the text stream, with
 // AdaLayerNorm_Final's (scale, shift) order. No key is masked (pad audio and pad text keys are attended, as in the
-// reference without attn_mask_enabled); audio rows are zeroed where ~mask on batch calls, text rows where text == -1
+// reference without attn_mask_enabled) unless the call is isolated (Ctx::isolate): then the keys are the two ranges
+// [0, dur) and [N, N + text length); audio rows are zeroed where ~mask on batch calls, text rows where text == -1
 // always (modules.py:700-703). No phase chain, LayerNorm fold or pad-row skip: the joint layout's live rows are not
 // a prefix, and the fold's producers / consumers would need the text stream's statistics buffers.
 static int backbone_mmdit(Ctx& c, hipStream_t st) {
@@ -1333,6 +1353,7 @@ static int backbone_mmdit(Ctx& c, hipStream_t st) {
     cv.bias = e->conv_b[0];
     cv.mode = 0;
     cv.y = b.c1;
+    cv.rowkeep = c.isolate ? keep : nullptr;  // (the reference passes no mask: pad rows bleed 15 frames per conv)
     {
       ProbeScope ps(e, KC_CONV, st, &c.site);
       KCK(conv_pos(bf, cv, st));
@@ -1417,7 +1438,12 @@ static int backbone_mmdit(Ctx& c, hipStream_t st) {
       at.S = c.S;
       at.H = H;
       at.L = Lj;
-      at.scale = 0.125f;
+      // isolated: the audio keys [0, dur) and the text keys [N, N + text length) of the joint sequence
+      if (c.isolate) {
+        at.kv_len = b.kvlen;
+        at.kv_start2 = c.N;
+        at.kv_len2 = b.tlen;
+      }
       at.prescaled = 1;
       at.store_wt = attention_store_wt(bf, at, store_want(c.store, KC_ATTN));
       count_store(at.store_wt);
@@ -1850,13 +1876,15 @@ static int check_ws(f5h_engine* e, int B, int N, int nfe, int use_cfg, void* w, 
   return 0;
 }
 // MMDiT calls (f5h_sample / f5h_forward): what the joint attention cannot serve
-static int check_mmdit_call(const f5h_engine* e, int nt, int batch_mask) {
+// (use_batch_mask == 2 masks both key ranges itself, whatever attn_mask_enabled says, and is served)
+static int check_mmdit_call(const f5h_engine* e, int nt, int batch_mask, int isolate) {
   if (e->a.backbone != F5H_MMDIT) return 0;
   if (nt <= 0) return fail(F5H_EINVAL, "MMDiT needs nt >= 1 text tokens");
-  if (e->a.attn_mask_enabled && batch_mask)
+  if (e->a.attn_mask_enabled && batch_mask && !isolate)
     return fail(F5H_EINVAL,
                 "MMDiT: attn_mask_enabled with a batch mask is not supported: the valid keys [0, dur) and [N, N + "
-                "text length) are not a prefix of the joint sequence, and the attention kernel masks a suffix only");
+                "text length) are not a prefix of the joint sequence, and the reference's masked mode is not wired to "
+                "the two-range attention (use_batch_mask 2 masks both ranges and isolates the batch)");
   return 0;
 }
 
@@ -1878,7 +1906,7 @@ static GraphKey prologue_key(const Ctx& c, const void* ws) {
   key.nt = c.nt;
   key.nfe = c.nfe;
   key.use_cfg = c.use_cfg;
-  key.batch_mask = c.batch_mask;
+  key.batch_mask = c.batch_mask + c.isolate;
   key.lnfold = c.lnfold;
   key.store = c.store;
   key.method = c.method;
@@ -1988,8 +2016,10 @@ static int sample_impl(f5h_engine* e, void* stream, const f5h_sample_args* a, in
   c.use_cfg = a->cfg_strength >= 1e-5f;
   c.S = c.use_cfg ? 2 * c.B : c.B;
   c.L = adaln_bb(e->a) ? c.N : c.N + 1;
+  if (a->use_batch_mask < 0 || a->use_batch_mask > 2) return fail(F5H_EINVAL, "use_batch_mask must be 0, 1 or 2");
   c.batch_mask = a->use_batch_mask ? 1 : 0;
-  RC(check_mmdit_call(e, c.nt, c.batch_mask));
+  c.isolate = a->use_batch_mask == 2 ? 1 : 0;
+  RC(check_mmdit_call(e, c.nt, c.batch_mask, c.isolate));
   RC(check_ws(e, c.B, c.N, c.nfe, c.use_cfg, workspace, workspace_bytes, c, method, c.steps));
   RC(chain_fault_check(e, c.st));
   ChainTicket ticket;  // (declared after `used`: its event is recorded first, both after every launch of the call)
@@ -2134,7 +2164,7 @@ static int run_steps(Ctx& c, const f5h_sample_args* a, const void* ws) {
   key.nt = e->a.backbone == F5H_MMDIT ? c.nt : 0;
   key.nfe = c.nfe;
   key.use_cfg = c.use_cfg;
-  key.batch_mask = c.batch_mask;
+  key.batch_mask = c.batch_mask + c.isolate;
   key.probe = e->probe_class;
   const bool split = e->split_cfg == 1;  // auto (2): one packed chain
   key.split = split;
@@ -2325,10 +2355,12 @@ int f5h_forward(f5h_engine* e, void* stream, const f5h_forward_args* a, void* wo
   c.drop_audio = (!c.use_cfg && a->drop_audio_cond) ? 1 : 0;
   c.drop_text = (!c.use_cfg && a->drop_text) ? 1 : 0;
   c.L = adaln_bb(e->a) ? c.N : c.N + 1;
+  if (a->use_batch_mask < 0 || a->use_batch_mask > 2) return fail(F5H_EINVAL, "use_batch_mask must be 0, 1 or 2");
   c.batch_mask = a->use_batch_mask ? 1 : 0;
+  c.isolate = a->use_batch_mask == 2 ? 1 : 0;
   if (e->a.backbone == F5H_DIT && a->N > 8192) return fail(F5H_EINVAL, "N exceeds the text position table (8192)");
   if (a->text_cache < 0 || a->text_cache > 2) return fail(F5H_EINVAL, "text_cache must be 0, 1 or 2");
-  RC(check_mmdit_call(e, c.nt, c.batch_mask));
+  RC(check_mmdit_call(e, c.nt, c.batch_mask, c.isolate));
   RC(check_ws(e, c.B, c.N, 1, c.use_cfg, workspace, workspace_bytes, c));
   RC(chain_fault_check(e, c.st));
   ChainTicket ticket;
@@ -2363,7 +2395,7 @@ int f5h_forward(f5h_engine* e, void* stream, const f5h_forward_args* a, void* wo
     key.nt = c.nt;
     key.nfe = 1;
     key.use_cfg = c.use_cfg;
-    key.batch_mask = c.batch_mask;
+    key.batch_mask = c.batch_mask + c.isolate;
     key.probe = e->probe_class;
     key.pad_skip = e->pad_skip;
     key.chain = c.chain;
@@ -2608,8 +2640,11 @@ int f5h_debug_tile_live(const int32_t* live_len, int32_t live_seq, int32_t M, in
 static int op_attention_impl(void* stream, int32_t compute, int32_t S, int32_t H, int32_t N, const float* Q,
                              const float* K, const float* V, const int32_t* kv_len, const int32_t* q_len,
                              int32_t q_prescaled, float* O, void* workspace, size_t workspace_bytes,
-                             int32_t o_split = 0, float* O2 = nullptr) {
+                             int32_t o_split = 0, float* O2 = nullptr, int32_t kv_start2 = 0,
+                             const int32_t* kv_len2 = nullptr) {
   if (S <= 0 || H <= 0 || N <= 0) return fail(F5H_EINVAL, "bad attention shape");
+  if (kv_len2 && (kv_start2 < 0 || kv_start2 > N))
+    return fail(F5H_EINVAL, "op_attention_ranges: kv_start2 must lie in [0, N]");
   if (o_split < 0 || o_split >= N || (o_split > 0 && !O2))
     return fail(F5H_EINVAL, "op_attention_split: o_split must lie in [0, N) and needs O2");
   if (compute < F5H_FP32 || compute > F5H_FP16) return fail(F5H_EINVAL, "bad compute mode");
@@ -2621,9 +2656,10 @@ static int op_attention_impl(void* stream, int32_t compute, int32_t S, int32_t H
   at.L = N;
   at.kv_len = kv_len;
   at.q_len = q_len;
-  at.scale = 0.125f;
   at.prescaled = q_prescaled ? 1 : 0;
   at.o_split = o_split;
+  at.kv_start2 = kv_start2;
+  at.kv_len2 = kv_len2;
   const int64_t n1 = o_split ? (int64_t)S * o_split * H * 64 : n;  // elements of the first output
   if (compute) {
     const size_t need = (size_t)n * 2 * 4 + 4 * 256;
@@ -2672,6 +2708,14 @@ int f5h_op_attention_split(void* stream, int32_t compute, int32_t S, int32_t H, 
                            size_t workspace_bytes) {
   return op_attention_impl(stream, compute, S, H, N, Q, K, V, kv_len, q_len, q_prescaled, O, workspace,
                            workspace_bytes, o_split, O2);
+}
+
+int f5h_op_attention_ranges(void* stream, int32_t compute, int32_t S, int32_t H, int32_t N, const float* Q,
+                            const float* K, const float* V, const int32_t* kv_len, int32_t kv_start2,
+                            const int32_t* kv_len2, const int32_t* q_len, int32_t q_prescaled, float* O,
+                            void* workspace, size_t workspace_bytes) {
+  return op_attention_impl(stream, compute, S, H, N, Q, K, V, kv_len, q_len, q_prescaled, O, workspace,
+                           workspace_bytes, 0, nullptr, kv_start2, kv_len2);
 }
 
 // ---- op-level entry points of the conv / norm / GEMM-epilogue kernels (tests/test_gpu_ops.py). Each validates
@@ -2775,9 +2819,9 @@ int f5h_op_norm(void* stream, int32_t compute, int32_t kind, int32_t h16, int32_
   return 0;
 }
 
-int f5h_op_dwconv_ln(void* stream, int32_t compute, int32_t S, int32_t L, int32_t C, const float* x,
-                     const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b, float* out,
-                     void* workspace, size_t workspace_bytes) {
+static int op_dwconv_ln_impl(void* stream, int32_t compute, int32_t S, int32_t L, int32_t C, const float* x,
+                             const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b,
+                             const int32_t* len, float* out, void* workspace, size_t workspace_bytes) {
   if (!op_compute_ok(compute)) return fail(F5H_EINVAL, "bad compute mode");
   if (S <= 0 || L <= 0 || C <= 0) return fail(F5H_EINVAL, "op_dwconv_ln: bad shape");
   if (C > 1024) return fail(F5H_EINVAL, "op_dwconv_ln needs C <= 1024");
@@ -2788,13 +2832,26 @@ int f5h_op_dwconv_ln(void* stream, int32_t compute, int32_t S, int32_t L, int32_
   OpWs ws(workspace, workspace_bytes);
   void* oop = compute ? ws.take((size_t)n * 2) : nullptr;
   OPWS_CHECK(ws, "op_dwconv_ln");
-  HIPCK(dwconv_ln(compute, x, S, L, C, dw_w, dw_b, ln_w, ln_b, oop ? oop : (void*)out, st));
+  HIPCK(dwconv_ln(compute, x, S, L, C, dw_w, dw_b, ln_w, ln_b, oop ? oop : (void*)out, st, len, S));
   if (oop) HIPCK(op_to_f32(compute, oop, n, out, st));
   return 0;
 }
+int f5h_op_dwconv_ln(void* stream, int32_t compute, int32_t S, int32_t L, int32_t C, const float* x,
+                     const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b, float* out,
+                     void* workspace, size_t workspace_bytes) {
+  return op_dwconv_ln_impl(stream, compute, S, L, C, x, dw_w, dw_b, ln_w, ln_b, nullptr, out, workspace,
+                           workspace_bytes);
+}
+int f5h_op_dwconv_ln_len(void* stream, int32_t compute, int32_t S, int32_t L, int32_t C, const float* x,
+                         const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b,
+                         const int32_t* len, float* out, void* workspace, size_t workspace_bytes) {
+  return op_dwconv_ln_impl(stream, compute, S, L, C, x, dw_w, dw_b, ln_w, ln_b, len, out, workspace,
+                           workspace_bytes);
+}
 
-int f5h_op_grn(void* stream, int32_t compute, int32_t S, int32_t L, int32_t C, const float* x, const float* gamma,
-               const float* beta, float* out, void* workspace, size_t workspace_bytes) {
+static int op_grn_impl(void* stream, int32_t compute, int32_t S, int32_t L, int32_t C, const float* x,
+                       const float* gamma, const float* beta, const int32_t* len, float* out, void* workspace,
+                       size_t workspace_bytes) {
   if (!op_compute_ok(compute)) return fail(F5H_EINVAL, "bad compute mode");
   if (S <= 0 || L <= 0 || C <= 0) return fail(F5H_EINVAL, "op_grn: bad shape");
   if (S > 65535 || (L + 63) / 64 > 65535) return fail(F5H_EINVAL, "op_grn: S and L / 64 are grid dimensions");
@@ -2805,9 +2862,17 @@ int f5h_op_grn(void* stream, int32_t compute, int32_t S, int32_t L, int32_t C, c
   float* scratch = reinterpret_cast<float*>(ws.take(((size_t)(L + 63) / 64 + 1) * S * C * sizeof(float)));
   void* oop = compute ? ws.take((size_t)n * 2) : nullptr;
   OPWS_CHECK(ws, "op_grn");
-  HIPCK(grn(compute, x, S, L, C, gamma, beta, scratch, oop ? oop : (void*)out, st));
+  HIPCK(grn(compute, x, S, L, C, gamma, beta, scratch, oop ? oop : (void*)out, st, len, S));
   if (oop) HIPCK(op_to_f32(compute, oop, n, out, st));
   return 0;
+}
+int f5h_op_grn(void* stream, int32_t compute, int32_t S, int32_t L, int32_t C, const float* x, const float* gamma,
+               const float* beta, float* out, void* workspace, size_t workspace_bytes) {
+  return op_grn_impl(stream, compute, S, L, C, x, gamma, beta, nullptr, out, workspace, workspace_bytes);
+}
+int f5h_op_grn_len(void* stream, int32_t compute, int32_t S, int32_t L, int32_t C, const float* x, const float* gamma,
+                   const float* beta, const int32_t* len, float* out, void* workspace, size_t workspace_bytes) {
+  return op_grn_impl(stream, compute, S, L, C, x, gamma, beta, len, out, workspace, workspace_bytes);
 }
 
 int f5h_op_gemm_epi(void* stream, const f5h_op_gemm_args* a, void* workspace, size_t workspace_bytes) {

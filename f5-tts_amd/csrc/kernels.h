@@ -158,25 +158,40 @@ int gemm_store_wt(int compute, int epi, const GemmArgs& a, int want);
 void store_policy_force(int mode);
 int store_policy_forced();
 
-// attention: Q,K,V [S,H,L,64] operand dtype; O [S,L,H*64] operand dtype.
+// attention: Q,K,V [S,H,L,64] operand dtype; O [S,L,H*64] operand dtype. The softmax scale is 1/sqrt(64) (kAttnScale).
+// Layout: a kernel argument of every attention launch, held at 120 bytes (the size it had before kv_start2 / kv_len2:
+// kv_start2 sits in the padding behind L, o_split beside prescaled, and the scale became a constant) -- 8 bytes more
+// move the hidden kernel arguments, which measured C2 +0.4 % with the default kernels' code unchanged (as GemmArgs'
+// layout note; DESIGN.md §5 'Isolated batches').
+constexpr float kAttnScale = 0.125f;
 struct AttnArgs {
   const void* q; const void* k; const void* v; void* o;
   int S, H, L;
+  int kv_start2;          // first row of the second key range (with kv_len2, below; in the padding behind L)
   const int32_t* kv_len;  // [S] or null: keys [kv_len[s], L) masked
   // [S] or null: query rows [q_len[s], L) are dead (their output is masked to 0 after to_out,
   // modules.py:551-553): query blocks wholly past q_len[s] exit at entry and leave O unwritten
   const int32_t* q_len;
-  float scale;            // 1/sqrt(64)
-  int prescaled;          // q already carries scale*log2(e): scores are in log2 units
+  int prescaled;          // q already carries kAttnScale*log2(e): scores are in log2 units
+  int o_split;            // split output (below)
   DevProbe probe;         // in-kernel launch timing (null slots: off)
   int force_safe;         // test hook: every workgroup reruns its key loop in the lazy-max form (attention.hip)
   int store_wt;           // store policy: 1 = O is stored write-through (16-bit kernel), 0 = plain; attention_store_wt
   // Split output (MMDiT joint attention; 0 = none): with 0 < o_split < L, row r < o_split of sequence s goes to
   // o [S, o_split, H*64] and row r >= o_split to o2 [S, L - o_split, H*64] row r - o_split. Only the output
-  // addressing changes (the Q load, the K/V ring and the softmax see one sequence of L rows).
-  int o_split;
+  // addressing changes (the Q load, the K/V ring and the softmax see one sequence of L rows). (o_split: above)
   void* o2;
+  // Second key range (MMDiT joint attention with masked keys; null = none): with kv_len2 [S] the valid keys of
+  // sequence s are [0, kv_len[s]) and [kv_start2, kv_start2 + kv_len2[s]) (kv_len null: the first range is
+  // [0, kv_start2)). The kernels clamp the first range to kv_start2 and the second to L, so no length reads outside
+  // the (sequence, head)'s rows. The key loop walks the first range's 64-key tiles from row 0, then the second
+  // range's from row kv_start2 (any row: the tile descriptor's base moves); a tile's DMA extent and key mask end at
+  // its own range's end, so rows outside the ranges are never read. Both ranges empty: the output rows are 0.
+  // Queries are unchanged (every row of [0, L), q_len, o_split). A separately compiled instantiation: launches
+  // without kv_len2 run the kernels they always ran.
+  const int32_t* kv_len2;
 };
+static_assert(sizeof(AttnArgs) == 120, "AttnArgs: keep the kernel argument's size (see the layout note)");
 hipError_t attention(int compute, const AttnArgs& a, hipStream_t st);
 int attention_store_wt(int compute, const AttnArgs& a, int want);  // as gemm_store_wt
 // test hook (f5h_attn_force_safe): 1 = every later 16-bit attention launch takes the SAFE rerun
@@ -237,11 +252,16 @@ struct TextUpArgs {
 };
 hipError_t text_upsample(const TextUpArgs& a, hipStream_t st);
 // depthwise conv k7 pad3 + bias then LayerNorm(affine, eps 1e-6) -> operand dtype. x: [S, L, C] fp32
+// len (device, or null): sequence s ends at row min(L, len[s % len_mod]) -- taps past it are zero, as taps past L
+// are; rows below it then have the bits of the sequence alone at that length (rows past it hold anything)
 hipError_t dwconv_ln(int compute, const float* x, int S, int L, int C, const float* dw_w, const float* dw_b,
-                     const float* ln_w, const float* ln_b, void* out, hipStream_t st);
+                     const float* ln_w, const float* ln_b, void* out, hipStream_t st, const int32_t* len = nullptr,
+                     int len_mod = 1);
 // GRN: sumsq[s,c] = sum_n x^2 ; then out = gamma*(x*Nx)+beta+x -> operand dtype
+// len (device, or null): the sum runs over rows below min(L, len[s % len_mod]) only (as dwconv_ln's)
 hipError_t grn(int compute, const float* x, int S, int L, int C, const float* gamma, const float* beta,
-               float* scratch /*[(ceil(L/64)+1)*S*C]*/, void* out, hipStream_t st);
+               float* scratch /*[(ceil(L/64)+1)*S*C]*/, void* out, hipStream_t st, const int32_t* len = nullptr,
+               int len_mod = 1);
 // A_ct [S*N, 128 + td] operand dtype: [where(cond_mask,cond,0) (zeros for uncond) pad 128 | text];
 // drop_audio / drop_text apply to the first (conditional) B sequences (single-branch forward)
 hipError_t build_ct(int compute, const float* cond, const uint8_t* cond_mask, const float* text_c,
@@ -329,6 +349,10 @@ hipError_t build_rowkeep(const int32_t* dur, int B, int S, int L, int off, uint8
 hipError_t build_textkeep(const int64_t* text, int B, int S, int nt, uint8_t* keep, hipStream_t st);
 // kv_len[s] = dur[s % B] + off
 hipError_t build_kvlen(const int32_t* dur, int B, int S, int off, int32_t* kv, hipStream_t st);
+// len[s] = 1 + the last position j with text[(s % B)*nt + j] != -1 (0 when all are filler), for S sequences: the
+// text key range of the MMDiT joint attention (AttnArgs::kv_len2). list_str_to_idx pads with fillers at the end
+// only, so this range is the reference's elementwise c_mask; a filler in the interior would stay attended.
+hipError_t build_textlen(const int64_t* text, int B, int S, int nt, int32_t* len, hipStream_t st);
 // h[s, 0, :] = temb (UNetT time token)
 hipError_t write_time_token(int compute, int h16, const float* temb, int S, int L, int d, void* h, hipStream_t st);
 // extract rows [s, 1..L-1] of pred -> dst [S, L-1, mel]; NaN when *fault (as final_where_out)

@@ -59,10 +59,13 @@ EXPORTS = (
     "f5h_op_attention",
     "f5h_op_attention_qlen",
     "f5h_op_attention_split",
+    "f5h_op_attention_ranges",
     "f5h_op_conv_pos",
     "f5h_op_norm",
     "f5h_op_dwconv_ln",
+    "f5h_op_dwconv_ln_len",
     "f5h_op_grn",
+    "f5h_op_grn_len",
     "f5h_op_gemm_epi",
     "f5h_op_text_upsample",
     "f5h_op_lnfold_uv",
@@ -247,6 +250,13 @@ def lib():
     if hasattr(L, "f5h_op_attention_split"):  # absent from an older build (has_mmdit)
         L.f5h_op_attention_split.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, sz]
         L.f5h_op_attention_split.restype = ctypes.c_int
+    if hasattr(L, "f5h_op_attention_ranges"):  # absent from an older build (has_isolate)
+        L.f5h_op_attention_ranges.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, sz]
+        L.f5h_op_attention_ranges.restype = ctypes.c_int
+        L.f5h_op_dwconv_ln_len.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz]
+        L.f5h_op_dwconv_ln_len.restype = ctypes.c_int
+        L.f5h_op_grn_len.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz]
+        L.f5h_op_grn_len.restype = ctypes.c_int
     if hasattr(L, "f5h_op_text_upsample"):  # absent from an older build (has_dit_options)
         L.f5h_op_text_upsample.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp]
         L.f5h_op_text_upsample.restype = ctypes.c_int
@@ -328,6 +338,12 @@ def has_mmdit() -> bool:
     """False for an older build (F5H_LIB) without f5h_op_attention_split: such a library has no MMDiT backbone, no
     split attention output and ignores the qkv_dst_len field of the GEMM op hook."""
     return hasattr(lib(), "f5h_op_attention_split")
+
+
+def has_isolate() -> bool:
+    """False for an older build (F5H_LIB) without f5h_op_attention_ranges: such a library has no isolated batches
+    (use_batch_mask == 2) and no second key range in attention."""
+    return hasattr(lib(), "f5h_op_attention_ranges")
 
 
 def has_ragged() -> bool:

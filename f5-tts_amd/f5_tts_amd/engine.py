@@ -77,15 +77,32 @@ def _mmdit_arch_struct(arch: dict, compute: str) -> _lib.Arch:
     return a
 
 
+def _is_isolated(use_batch_mask) -> bool:
+    return use_batch_mask is not True and use_batch_mask == 2
+
+
 def _refuse_mmdit_masked(arch: dict, use_batch_mask) -> None:
-    """MMDiT with attn_mask_enabled and a batch mask (B > 1): the joint sequence's valid keys are [0, dur) and
-    [N, N + text length), not a prefix, and the attention kernel masks a suffix only. Refused before any device work
-    (f5h_sample / f5h_forward return F5H_EINVAL for the same call)."""
-    if arch["backbone"] == "MMDiT" and arch.get("attn_mask_enabled") and use_batch_mask:
+    """MMDiT with attn_mask_enabled and a plain batch mask (B > 1): the joint sequence's valid keys are [0, dur) and
+    [N, N + text length), not a prefix, and the reference's masked mode is not wired to the two-range attention.
+    Refused before any device work (f5h_sample / f5h_forward return F5H_EINVAL for the same call). An isolated call
+    (use_batch_mask == 2) masks both ranges itself, whatever the flag says, and is served."""
+    if arch["backbone"] == "MMDiT" and arch.get("attn_mask_enabled") and use_batch_mask \
+            and not _is_isolated(use_batch_mask):
         raise NotImplementedError(
             "MMDiT with attn_mask_enabled=True and a batch mask is not supported: the valid keys of the joint "
             "text-audio sequence are not a prefix and the attention kernel masks a suffix only (DESIGN.md §8); "
-            "run single utterances, or the model without attn_mask_enabled")
+            "run single utterances, isolated batches (isolate=True), or the model without attn_mask_enabled")
+
+
+def _mask_mode(arch: dict, use_batch_mask) -> int:
+    """f5h_sample_args.use_batch_mask of a call: 0 none, 1 the batch mask, 2 the batch mask plus isolation (every
+    utterance computed as if it were sampled alone). An older library (F5H_LIB) without f5h_op_attention_ranges has no
+    isolation: refused before any device work."""
+    mode = 2 if _is_isolated(use_batch_mask) else int(bool(use_batch_mask))
+    if mode == 2 and not _lib.has_isolate():
+        raise NotImplementedError("the loaded libf5h.so has no f5h_op_attention_ranges (an older build): it cannot "
+                                  "run isolated batches (isolate=True / use_batch_mask=2)")
+    return mode
 
 
 def _ode_method(method: str) -> int:
@@ -251,8 +268,10 @@ class Engine:
         cond f32 [B,N,mel], cond_mask bool/u8 [B,N], text int64 [B,nt], duration int [B],
         y0 f32 [B,N,mel]; t_grid: host sequence of nfe+1 floats, the step grid. method: the fixed-grid
         solver, "euler", "midpoint" or "rk4" (1, 2, 4 backbone evaluations per step; f5h_sample_ode);
-        the trajectory holds the nfe+1 grid points for every method."""
+        the trajectory holds the nfe+1 grid points for every method. use_batch_mask: False / True, or 2 for the
+        batch mask plus isolation (rows below duration[b] do not depend on the rest of the batch; f5h.h)."""
         _refuse_mmdit_masked(self.arch, use_batch_mask)
+        mode = _mask_mode(self.arch, use_batch_mask)
         B, N, mel = cond.shape
         nt = text.shape[1]
         tg = np.ascontiguousarray(np.asarray(t_grid, dtype=np.float32))
@@ -280,7 +299,7 @@ class Engine:
                                                          dur.data_ptr(), y0.data_ptr())
         a.t_grid = tg.ctypes.data
         a.cfg_strength = float(cfg_strength)
-        a.use_batch_mask = int(bool(use_batch_mask))
+        a.use_batch_mask = mode
         a.out = out.data_ptr()
         a.trajectory = traj.data_ptr() if traj is not None else None
         with torch.cuda.device(self.device), wlock:
@@ -302,8 +321,9 @@ class Engine:
         cfg_infer: packed cond/uncond -> pred [2B,N,mel]; else one branch -> [B,N,mel] honouring
         drop_audio_cond / drop_text. t: a python float, or a one-element device tensor (read on the
         stream, no host sync). text_cache: 0 = compute the text embedding for this call, 1 = compute
-        and keep it in `workspace`, 2 = reuse the one kept there (dit.py:294-317)."""
+        and keep it in `workspace`, 2 = reuse the one kept there (dit.py:294-317). use_batch_mask: as `sample`."""
         _refuse_mmdit_masked(self.arch, use_batch_mask)
+        mode = _mask_mode(self.arch, use_batch_mask)
         B, N, mel = x.shape
         nt = text.shape[1]
         x = x.to(self.device, torch.float32).contiguous()
@@ -327,7 +347,7 @@ class Engine:
         a.t = 0.0 if t_dev is not None else float(t)
         a.t_dev = t_dev.data_ptr() if t_dev is not None else None
         a.text_cache = int(text_cache)
-        a.use_batch_mask = int(bool(use_batch_mask))
+        a.use_batch_mask = mode
         a.pred = pred.data_ptr()
         a.cfg_infer = int(bool(cfg_infer))
         a.drop_audio_cond = int(bool(drop_audio_cond))
@@ -433,6 +453,26 @@ def op_attention_split(Q, K, V, o_split, kv_len=None, q_len=None, compute="bf16"
     return (O, O2, ws) if return_ws else (O, O2)
 
 
+def op_attention_ranges(Q, K, V, kv_len=None, kv_start2=0, kv_len2=None, q_len=None, compute="bf16",
+                        q_prescaled=False):
+    """op_attention over two key ranges per sequence (f5h_op_attention_ranges): the valid keys of sequence s are
+    [0, kv_len[s]) and [kv_start2, kv_start2 + kv_len2[s]). kv_len2 None: f5h_op_attention_qlen's kernels."""
+    if not _lib.has_isolate():
+        raise RuntimeError("the loaded libf5h.so has no f5h_op_attention_ranges (an older build)")
+    S, H, N, D = Q.shape
+    assert D == 64
+    O = torch.zeros(S, N, H * 64, dtype=torch.float32, device=Q.device)
+    ws = torch.zeros(Q.numel() * 8 + 1024, dtype=torch.uint8, device=Q.device)
+    i32 = lambda t: None if t is None else torch.as_tensor(t).to(Q.device, torch.int32).contiguous()  # noqa: E731
+    kv, kv2, ql = i32(kv_len), i32(kv_len2), i32(q_len)
+    _lib.check(_lib.lib().f5h_op_attention_ranges(_lib.stream_handle(Q.device), _lib.COMPUTE[compute], S, H, N,
+                                                  Q.contiguous().data_ptr(), K.contiguous().data_ptr(),
+                                                  V.contiguous().data_ptr(), _lib.ptr(kv), int(kv_start2),
+                                                  _lib.ptr(kv2), _lib.ptr(ql), int(bool(q_prescaled)), O.data_ptr(),
+                                                  ws.data_ptr(), ws.numel()), "f5h_op_attention_ranges")
+    return O
+
+
 def _f32(t, dev=None):
     return None if t is None else t.to(device=dev or t.device, dtype=torch.float32).contiguous()
 
@@ -473,26 +513,47 @@ def op_norm(kind, h, p0, p1=None, h16=False, compute="bf16"):
     return out
 
 
-def op_dwconv_ln(x, dw_w, dw_b, ln_w, ln_b, compute="bf16"):
-    """LayerNorm(dwconv7(x) + dw_b) * ln_w + ln_b; x [S,L,C], dw_w [C,7]."""
+def op_dwconv_ln(x, dw_w, dw_b, ln_w, ln_b, compute="bf16", seq_len=None):
+    """LayerNorm(dwconv7(x) + dw_b) * ln_w + ln_b; x [S,L,C], dw_w [C,7]. seq_len [S] (f5h_op_dwconv_ln_len):
+    sequence s ends at row seq_len[s], taps past it are zero."""
     S, L, C = x.shape
     dev = x.device
     x, dw_w, dw_b, ln_w, ln_b = (_f32(t, dev) for t in (x, dw_w, dw_b, ln_w, ln_b))
     out = torch.empty(S, L, C, dtype=torch.float32, device=dev)
     ws = torch.empty(x.numel() * 2 + 1024, dtype=torch.uint8, device=dev)
+    if seq_len is not None:
+        if not _lib.has_isolate():
+            raise RuntimeError("the loaded libf5h.so has no f5h_op_dwconv_ln_len (an older build)")
+        ln = torch.as_tensor(seq_len).to(dev, torch.int32).contiguous()
+        assert ln.numel() == S
+        _lib.check(_lib.lib().f5h_op_dwconv_ln_len(_lib.stream_handle(dev), _lib.COMPUTE[compute], S, L, C,
+                                                   x.data_ptr(), dw_w.data_ptr(), dw_b.data_ptr(), ln_w.data_ptr(),
+                                                   ln_b.data_ptr(), ln.data_ptr(), out.data_ptr(), ws.data_ptr(),
+                                                   ws.numel()), "f5h_op_dwconv_ln_len")
+        return out
     _lib.check(_lib.lib().f5h_op_dwconv_ln(_lib.stream_handle(dev), _lib.COMPUTE[compute], S, L, C, x.data_ptr(),
                                            dw_w.data_ptr(), dw_b.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(),
                                            out.data_ptr(), ws.data_ptr(), ws.numel()), "f5h_op_dwconv_ln")
     return out
 
 
-def op_grn(x, gamma, beta, compute="bf16"):
-    """GRN over time: gamma * (x * Nx) + beta + x; x [S,L,C]."""
+def op_grn(x, gamma, beta, compute="bf16", seq_len=None):
+    """GRN over time: gamma * (x * Nx) + beta + x; x [S,L,C]. seq_len [S] (f5h_op_grn_len): the norm of sequence s
+    runs over its rows below seq_len[s] only."""
     S, L, C = x.shape
     dev = x.device
     x, gamma, beta = (_f32(t, dev) for t in (x, gamma, beta))
     out = torch.empty(S, L, C, dtype=torch.float32, device=dev)
     ws = torch.empty(((L + 63) // 64 + 1) * S * C * 4 + x.numel() * 2 + 1024, dtype=torch.uint8, device=dev)
+    if seq_len is not None:
+        if not _lib.has_isolate():
+            raise RuntimeError("the loaded libf5h.so has no f5h_op_grn_len (an older build)")
+        ln = torch.as_tensor(seq_len).to(dev, torch.int32).contiguous()
+        assert ln.numel() == S
+        _lib.check(_lib.lib().f5h_op_grn_len(_lib.stream_handle(dev), _lib.COMPUTE[compute], S, L, C, x.data_ptr(),
+                                             gamma.data_ptr(), beta.data_ptr(), ln.data_ptr(), out.data_ptr(),
+                                             ws.data_ptr(), ws.numel()), "f5h_op_grn_len")
+        return out
     _lib.check(_lib.lib().f5h_op_grn(_lib.stream_handle(dev), _lib.COMPUTE[compute], S, L, C, x.data_ptr(),
                                      gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel()),
                "f5h_op_grn")

@@ -275,13 +275,18 @@ def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_ty
 def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocoder, mel_spec_type="vocos",
                         progress=None, target_rms=0.1, cross_fade_duration=0.15, nfe_step=32, cfg_strength=2.0,
                         sway_sampling_coef=-1, speed=1, fix_duration=None, device=None, streaming=False,
-                        chunk_size=2048):
+                        chunk_size=2048, batch_chunks=False):
     """utils_infer.py:440-596. Generator: yields `(wave, sr, spectrogram)` once (or, with
     `streaming`, `(wave_chunk, sr)` pieces of each batch in order). Per batch: duration
     = ref frames + ref frames / ref bytes * gen bytes / speed (speed 0.3 for < 10-byte text),
     `model_obj.sample` on the raw reference wave, keep the generated frames, Vocos decode,
     undo the RMS boost. Batches run on a thread pool as the reference does (each call is
-    re-entrant on the engine)."""
+    re-entrant on the engine).
+    `batch_chunks=True` with more than one batch: the chunks go as ONE isolated batch instead of concurrent
+    single calls -- the prompt's log-mel once (`model_obj.mel_spec`), one `model_obj.sample(..., isolate=True)` with
+    host durations / lens, one `vocoder.decode_ragged`; no thread pool. An isolated batch computes every chunk as
+    if it were sampled alone, so the wave, the spectrogram and the streaming pieces equal the thread-pool path's
+    (given the same noise per chunk)."""
     if mel_spec_type != "vocos":
         raise NotImplementedError("only the vocos mel/vocoder pair is on the HIP path")
     audio, sr = ref_audio
@@ -300,16 +305,19 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
     if len(ref_text[-1].encode("utf-8")) == 1:
         ref_text = ref_text + " "
 
-    def _infer_basic(gen_text):
+    ref_audio_len = audio.shape[-1] // hop_length
+
+    def _duration(gen_text):
         local_speed = 0.3 if len(gen_text.encode("utf-8")) < 10 else speed
-        final_text_list = convert_char_to_pinyin([ref_text + gen_text])
-        ref_audio_len = audio.shape[-1] // hop_length
         if fix_duration is not None:
-            duration = int(fix_duration * target_sample_rate / hop_length)
-        else:
-            ref_text_len = len(ref_text.encode("utf-8"))
-            gen_text_len = len(gen_text.encode("utf-8"))
-            duration = ref_audio_len + int(ref_audio_len / ref_text_len * gen_text_len / local_speed)
+            return int(fix_duration * target_sample_rate / hop_length)
+        ref_text_len = len(ref_text.encode("utf-8"))
+        gen_text_len = len(gen_text.encode("utf-8"))
+        return ref_audio_len + int(ref_audio_len / ref_text_len * gen_text_len / local_speed)
+
+    def _infer_basic(gen_text):
+        final_text_list = convert_char_to_pinyin([ref_text + gen_text])
+        duration = _duration(gen_text)
         with torch.inference_mode():
             generated, _ = model_obj.sample(cond=audio, text=final_text_list, duration=duration, steps=nfe_step,
                                             cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef)
@@ -321,7 +329,41 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
             wav = wav.squeeze().cpu().numpy()
         return wav, generated
 
+    def _infer_batched(gen_texts):
+        """All chunks as one isolated batch: [(wave, generated [mel, frames])] in chunk order."""
+        texts = [convert_char_to_pinyin([ref_text + t])[0] for t in gen_texts]
+        n = len(gen_texts)
+        with torch.inference_mode():
+            cond = model_obj.mel_spec(audio).permute(0, 2, 1)  # [1, frames, mel], as CFM.sample forms it per call
+            frames = cond.shape[1]
+            # the duration rule of CFM.sample (cfm.py:135-139) on the host: the frames each chunk's own call would have
+            total = [min(max(max(len(t), frames) + 1, _duration(g)), 65536) for t, g in zip(texts, gen_texts)]
+            generated, _ = model_obj.sample(cond=cond.expand(n, -1, -1).contiguous(), text=texts,
+                                            duration=torch.tensor(total, dtype=torch.long),
+                                            lens=torch.tensor([frames] * n, dtype=torch.long), steps=nfe_step,
+                                            cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef,
+                                            isolate=True)
+            del _
+            generated = generated.to(torch.float32)
+            wavs = vocoder.decode_ragged(generated, [ref_audio_len] * n, [t - ref_audio_len for t in total])
+            res = []
+            for i, wav in enumerate(wavs):
+                if rms < target_rms:
+                    wav = wav * rms / target_rms
+                res.append((wav.cpu().numpy(), generated[i, ref_audio_len:total[i]].T.contiguous()))
+        return res
+
     it = (lambda xs: progress.tqdm(xs)) if progress is not None else (lambda xs: xs)
+    if batch_chunks and len(gen_text_batches) > 1:
+        res = _infer_batched(list(gen_text_batches))
+        if streaming:
+            for wav, _g in it(res):
+                for j in range(0, len(wav), chunk_size):
+                    yield wav[j: j + chunk_size], target_sample_rate
+            return
+        yield (cross_fade([w for w, _g in res], cross_fade_duration), target_sample_rate,
+               np.concatenate([g.cpu().numpy() for _w, g in res], axis=1))
+        return
     if streaming:
         for gen_text in it(gen_text_batches):
             wav, generated = _infer_basic(gen_text)
@@ -349,7 +391,8 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
 
 
 def infer_batch(items, model_obj, vocoder, *, nfe_step=nfe_step, cfg_strength=cfg_strength,
-                sway_sampling_coef=sway_sampling_coef, speed=1.0, seed=None, target_rms=target_rms, max_batch=32):
+                sway_sampling_coef=sway_sampling_coef, speed=1.0, seed=None, target_rms=target_rms, max_batch=32,
+                isolate=False):
     """Batch synthesis to waveforms, the reference's eval recipe (eval/utils_eval.py:109-148 and
     eval/eval_infer_batch.py:188-212) on ragged batches. `items`: `(ref_audio, ref_text, gen_text)` per utterance,
     `ref_audio` a WAV path or an `(audio [C, n] tensor, sr)` tuple as in `infer_process`. Per item: mono, RMS boost
@@ -358,6 +401,8 @@ def infer_batch(items, model_obj, vocoder, *, nfe_step=nfe_step, cfg_strength=cf
     frames. The items are grouped into length buckets of at most `max_batch` (`parallel.bucket`); each bucket is one
     `model_obj.mel_spec.forward_ragged`, one `model_obj.sample(cond, text, duration, lens=...)` with host lengths and
     one `vocoder.decode_ragged(out, ref, total - ref)`; the RMS boost is undone only where it was applied.
+    `isolate=True`: `sample(..., isolate=True)`, every utterance computed as if it were sampled alone, so the result
+    no longer depends on the bucketing (which utterances share a batch, and `max_batch`).
     Returns `[(wave, 24000)]` in input order, `wave` a 1-D float32 numpy array of (total - ref - 1) * 256 samples."""
     from . import parallel
 
@@ -393,7 +438,8 @@ def infer_batch(items, model_obj, vocoder, *, nfe_step=nfe_step, cfg_strength=cf
             generated, _ = model_obj.sample(cond=cond, text=[prep[i]["text"] for i in b],
                                             duration=torch.tensor(total, dtype=torch.long),
                                             lens=torch.tensor(ref, dtype=torch.long), steps=nfe_step,
-                                            cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed)
+                                            cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed,
+                                            **({"isolate": True} if isolate else {}))
             del _
             for i, wav in zip(b, vocoder.decode_ragged(generated, ref, [t - r for t, r in zip(total, ref)])):
                 if prep[i]["rms"] < target_rms:

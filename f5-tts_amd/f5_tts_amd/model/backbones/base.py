@@ -128,7 +128,7 @@ class EngineBackbone(nn.Module):
 
     # ------------------------------------------------------------------ plugin forward
     def forward(self, x, cond, text, time, mask=None, drop_audio_cond=False, drop_text=False, cfg_infer=False,
-                cache=False, compute: str | None = None):
+                cache=False, compute: str | None = None, isolate: bool = False):
         """DiT.forward / UNetT.forward through the engine (dit.py:319-370, unett.py:244-307).
 
         cfg_infer=True: the packed cond/uncond forward of CFM.sample (cfm.py:181-191) -> [2B, N, mel];
@@ -139,13 +139,14 @@ class EngineBackbone(nn.Module):
         `time` is read on the stream (no host sync). `cache=True`: the first call of this thread's
         session computes the text embedding (both branches) and keeps it, later calls reuse it until
         clear_cache(), as dit.py:294-317 does; sessions are keyed by shape, the MAX_SESSIONS most recently
-        used per thread are kept."""
+        used per thread are kept. `isolate=True` (with a mask and B > 1): every sample is computed as if it were alone
+        in the batch (f5h.h use_batch_mask == 2), so its rows below mask.sum() do not depend on the other samples."""
         B, N = x.shape[:2]
         compute = compute or compute_for_dtype(next(self.parameters()).dtype)
         eng = self.get_engine(compute, x.device)
         dur = mask.sum(1) if mask is not None else torch.full((B,), N, device=x.device)
         ones = torch.ones(B, N, dtype=torch.uint8, device=x.device)
-        use_mask = mask is not None
+        use_mask = 2 if (isolate and mask is not None and B > 1) else mask is not None
         flags = dict(cfg_infer=cfg_infer, drop_audio_cond=drop_audio_cond, drop_text=drop_text)
         if not torch.is_tensor(time) or time.numel() == 1:
             tval = time if torch.is_tensor(time) else float(time)

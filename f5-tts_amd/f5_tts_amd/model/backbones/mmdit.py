@@ -7,9 +7,10 @@ cat(x, cond) + conv position embedding) and MM-DiT blocks that project both stre
 their own weights, rotate them independently, attend them as one sequence and split them
 again; the last block only pre-normalises the text stream. The forward pass is the HIP engine.
 
-`attn_mask_enabled=True` together with a batch mask (B > 1) raises NotImplementedError: the
+`attn_mask_enabled=True` together with a plain batch mask (B > 1) raises NotImplementedError: the
 joint sequence's valid keys are not a prefix. With B = 1 or no mask the flag has
-no effect in the reference either and is accepted.
+no effect in the reference either and is accepted; an isolated call (`isolate=True`) masks the audio
+range [0, dur) and the text range [N, N + text length) itself and is served.
 """
 
 from __future__ import annotations
@@ -32,10 +33,10 @@ class MMDiT(EngineBackbone):
         ))
 
     def forward(self, x, cond, text, time, mask=None, drop_audio_cond=False, drop_text=False, cfg_infer=False,
-                cache=False, compute: str | None = None):
-        if self.arch.get("attn_mask_enabled") and mask is not None:
+                cache=False, compute: str | None = None, isolate: bool = False):
+        if self.arch.get("attn_mask_enabled") and mask is not None and not (isolate and x.shape[0] > 1):
             from ...engine import _refuse_mmdit_masked
 
             _refuse_mmdit_masked(self.arch, True)  # before any device work (engine creation included)
         return super().forward(x, cond, text, time, mask=mask, drop_audio_cond=drop_audio_cond, drop_text=drop_text,
-                               cfg_infer=cfg_infer, cache=cache, compute=compute)
+                               cfg_infer=cfg_infer, cache=cache, compute=compute, isolate=isolate)

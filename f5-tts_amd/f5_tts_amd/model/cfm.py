@@ -107,16 +107,21 @@ class CFM(nn.Module):
     def sample(self, cond, text, duration, *, lens=None, steps=32, cfg_strength=1.0, sway_sampling_coef=None,
                seed: int | None = None, max_duration=65536, vocoder: Callable | None = None, use_epss=True,
                no_ref_audio=False, duplicate_test=False, t_inter=0.1, edit_mask=None, y0=None,
-               keep_trajectory: bool = True):
+               keep_trajectory: bool = True, isolate: bool = False):
         """Same arguments/returns as the reference `CFM.sample`; extra keyword `y0` supplies the
-        initial noise explicitly (parity tests), `keep_trajectory=False` skips the [steps+1,...] copy."""
+        initial noise explicitly (parity tests), `keep_trajectory=False` skips the [steps+1,...] copy.
+        `isolate=True`: every utterance of a batch is sampled as if it were alone (f5h.h use_batch_mask == 2), so its
+        frames below its duration do not depend on what else is in the batch (the reference's padded batch leaks: pad
+        keys, GRN over the padded axis, unmasked conv position embeddings); with one utterance it is the plain call."""
         if self.training:
             self.eval()
         arch = getattr(self.transformer, "arch", None)
-        if arch is not None:  # MMDiT with attn_mask_enabled and B > 1: refused before any device work
-            from ..engine import _refuse_mmdit_masked
+        if arch is not None:  # MMDiT with attn_mask_enabled and a plain batch mask, or isolation on an older library:
+            from ..engine import _mask_mode, _refuse_mmdit_masked  # refused before any device work
 
-            _refuse_mmdit_masked(arch, cond.shape[0] > 1)
+            mode = (2 if isolate else 1) if cond.shape[0] > 1 else 0
+            _refuse_mmdit_masked(arch, mode)
+            _mask_mode(arch, mode)
         pdtype = next(self.parameters()).dtype
         if cond.ndim == 2:  # raw wave -> mel (cfm.py:106-109)
             cond = self.mel_spec(cond)
@@ -169,6 +174,8 @@ class CFM(nn.Module):
             cond = torch.zeros_like(cond)
         cond_mask = F.pad(cond_mask, (0, max_duration - cond_mask.shape[-1]), value=False)
         use_batch_mask = batch > 1  # cfm.py:155-158
+        if isolate and use_batch_mask:
+            use_batch_mask = 2
 
         if y0 is None:  # noise recipe of cfm.py:196-201 (per utterance, same seed each)
             ys = []

@@ -42,11 +42,14 @@ enum f5h_status {
  * one sequence of N + nt rows and split again. The last block only pre-normalises the text stream (context_pre_only).
  * The arch must have text_dim == dim, conv_layers == 0, pe_attn_head == 0, long_skip_connection == 0,
  * text_average_upsampling == 0 and depth >= 1 (F5H_EINVAL names the field); qk_norm adds c_q_norm / c_k_norm.
- * nt >= 1. attn_mask_enabled together with use_batch_mask is refused by f5h_sample / f5h_forward (F5H_EINVAL): the
+ * nt >= 1. attn_mask_enabled together with use_batch_mask == 1 is refused by f5h_sample / f5h_forward (F5H_EINVAL): the
  * valid keys [0, dur) and [N, N + tlen) are not a prefix of the joint sequence; without a batch mask
- * the flag has no effect, as in the reference. Accepted without effect on such an engine: f5h_set_chain,
- * f5h_set_ln_fold, f5h_set_pad_skip and f5h_set_cfg_streams (the joint layout has no live-row prefix, and the block
- * step always runs as one chain of separate launches). */
+ * the flag has no effect, as in the reference. use_batch_mask == 2 (below) masks both ranges itself, whatever the
+ * flag says, and is served: tlen = 1 + the last non-filler text position (fillers stand at the end of a text,
+ * list_str_to_idx, where this is the reference's elementwise c_mask; a filler in the interior stays attended).
+ * Accepted without effect on such an engine: f5h_set_chain, f5h_set_ln_fold, f5h_set_pad_skip and
+ * f5h_set_cfg_streams (the joint layout has no live-row prefix, and the block step always runs as one chain of
+ * separate launches). */
 enum f5h_backbone { F5H_DIT = 0, F5H_UNETT = 1, F5H_MMDIT = 2 };
 /* Operand dtype of the GEMM / attention / conv MFMAs. Accumulation, norm and softmax statistics and
  * the ODE state are fp32 in every mode; the residual stream is fp32 in the fp32 mode and, in the 16-bit
@@ -149,7 +152,16 @@ typedef struct f5h_sample_args {
   const float* y0;           /* [B,N,mel] initial noise, zero-padded (cfm.py:196-201) */
   const float* t_grid;       /* HOST [nfe+1] time grid, EPSS/linspace + sway (cfm.py:211-216) */
   float cfg_strength;        /* < 1e-5 disables the packed uncond branch (cfm.py:167) */
-  int32_t use_batch_mask;    /* 1 when B>1 (cfm.py:155-158) */
+  /* 1 when B>1 (cfm.py:155-158). 2 = the batch mask plus isolation (a library that exports f5h_op_attention_ranges):
+   * every utterance is computed as if it were sampled alone, so its rows below duration[b] do not depend on what else
+   * is in the batch (the reference's padded batch does: pad keys are attended without attn_mask_enabled, GRN norms over
+   * the padded time axis, UNetT / MMDiT run conv_pos_embed unmasked, MMDiT attends filler text keys). Isolated, the
+   * row mask goes on both conv_pos launches of every backbone, the key lengths on every attention whatever
+   * attn_mask_enabled says (MMDiT: the two ranges [0, dur) and [N, N + tlen)), and the DiT text embedding's depthwise
+   * conv and GRN stop at duration[b]. DiT and UNetT rows then equal the utterance's own B = 1 call bit for bit (with
+   * the LayerNorm fold off there, as masked batches never fold); MMDiT to rounding (the text keys' tile partition
+   * differs). Other values: F5H_EINVAL. The same holds for f5h_forward_args.use_batch_mask. */
+  int32_t use_batch_mask;
   float* out;                /* [B,N,mel] result: where(cond_mask, cond, y_final) (cfm.py:223) */
   float* trajectory;         /* [nfe+1,B,N,mel] or NULL (odeint output, cfm.py:218) */
 } f5h_sample_args;
@@ -338,6 +350,16 @@ int f5h_op_attention_qlen(void* stream, int32_t compute, int32_t S, int32_t H, i
                           const float* K, const float* V, const int32_t* kv_len, const int32_t* q_len,
                           int32_t q_prescaled, float* O, void* workspace, size_t workspace_bytes);
 
+/* f5h_op_attention_qlen with a second key range: with kv_len2 [S] (device) the valid keys of sequence s are
+ * [0, kv_len[s]) and [kv_start2, kv_start2 + kv_len2[s]) (kv_len NULL: [0, kv_start2)); 0 <= kv_start2 <= N, any row.
+ * The first range is clamped to kv_start2 and the second to N. K / V rows outside the ranges are never read (they may
+ * hold NaN); a sequence with both ranges empty gets 0. kv_len2 NULL is f5h_op_attention_qlen itself, the same
+ * kernels. Its presence tells a caller that the library serves use_batch_mask == 2. */
+int f5h_op_attention_ranges(void* stream, int32_t compute, int32_t S, int32_t H, int32_t N, const float* Q,
+                            const float* K, const float* V, const int32_t* kv_len, int32_t kv_start2,
+                            const int32_t* kv_len2, const int32_t* q_len, int32_t q_prescaled, float* O,
+                            void* workspace, size_t workspace_bytes);
+
 /* f5h_op_attention_qlen with a split output (MMDiT joint attention): with 0 < o_split < N, row r < o_split of
  * sequence s goes to O [S, o_split, H*64] and row r >= o_split to O2 [S, N - o_split, H*64] row r - o_split; o_split
  * == 0 is f5h_op_attention_qlen (O2 unused). In the 16-bit modes the 16-bit O and O2 sit back to back at workspace
@@ -379,6 +401,14 @@ int f5h_op_dwconv_ln(void* stream, int32_t compute, int32_t S, int32_t L, int32_
  * x [S,L,C]; gamma, beta [C]; out [S,L,C] (operand dtype). */
 int f5h_op_grn(void* stream, int32_t compute, int32_t S, int32_t L, int32_t C, const float* x, const float* gamma,
                const float* beta, float* out, void* workspace, size_t workspace_bytes);
+/* The two with a length per sequence, len [S] (device; NULL: the plain ops): sequence s ends at row min(L, len[s]).
+ * The depthwise conv's taps past it are zero and GRN's norm sums rows below it only, so rows below len[s] equal, bit
+ * for bit, the plain op on that sequence alone at L = len[s]. Rows past it are written from whatever x holds there. */
+int f5h_op_dwconv_ln_len(void* stream, int32_t compute, int32_t S, int32_t L, int32_t C, const float* x,
+                         const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b,
+                         const int32_t* len, float* out, void* workspace, size_t workspace_bytes);
+int f5h_op_grn_len(void* stream, int32_t compute, int32_t S, int32_t L, int32_t C, const float* x, const float* gamma,
+                   const float* beta, const int32_t* len, float* out, void* workspace, size_t workspace_bytes);
 
 /* f5h_op_linear with any GEMM epilogue (the LayerNorm / RMSNorm fold forms: the struct's trailing fields). epi:
  *   0 STORE       C = acc + bias                          1 SILU          C = silu(acc + bias)
