@@ -83,7 +83,11 @@ F5H_DEV void attn_block(int& qb, int& bh) {
 // range's tiles [0, nt1), rows kt * 64 up to klen, then the second range's, rows start2 + (kt - nt1) * 64 up to
 // end2: the ring, the waits and the running max see one sequence of ntile tiles. A tile's DMA extent ends at its
 // range's end (not at L), so rows between the ranges read as zero and are never loaded.
-template <typename T, bool PRESCALED, int NW, bool RSM, bool WT = false, bool RG = false>
+// RO: ragged output (AttnArgs::o_split == kAttnRagged; a separately compiled kernel). The panels stay [S, H, a.L, 64];
+// the sequence's own length kv_len[s] takes L's place everywhere else (key range, DMA extents, Q clamp, store guard),
+// so a (sequence, head) runs the instructions of the plain kernel on that sequence alone and rows of the panel past
+// its length are never read; O row n of sequence s is packed row seg_off[s] + n.
+template <typename T, bool PRESCALED, int NW, bool RSM, bool WT = false, bool RG = false, bool RO = false>
 __global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
   typedef Op16<T> OP;
   typedef typename OP::v8 v8;
@@ -103,12 +107,20 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
   // the XCDs round-robin so every XCD holds a share of every length (all blocks of a pair stay on one XCD)
   if (a.q_len) bh = spread8(bh, gridDim.y);
   const int s_idx = bh / a.H, head = bh - s_idx * a.H;
-  const int L = a.L;
+  int Lseq = a.L;
+  if constexpr (RO) Lseq = __builtin_amdgcn_readfirstlane(max(0, min(a.L, a.kv_len[s_idx])));
+  const int L = Lseq;
   if (a.q_len && qb * (32 * NW) >= a.q_len[s_idx]) {  // dead query block (pad rows only): nothing to write
     probe_exit(a.probe, probe_t);
     return;
   }
-  const int64_t base = (int64_t)bh * L * 64;
+  if constexpr (RO) {
+    if (qb * (32 * NW) >= L) {  // (q_len is the same length on the ragged path; an empty sequence writes nothing)
+      probe_exit(a.probe, probe_t);
+      return;
+    }
+  }
+  const int64_t base = (int64_t)bh * (RO ? a.L : L) * 64;
   const T* Q = reinterpret_cast<const T*>(a.q) + base;
   const T* K = reinterpret_cast<const T*>(a.k) + base;
   const T* V = reinterpret_cast<const T*>(a.v) + base;
@@ -497,7 +509,9 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
     // 32 rows may straddle sp, so the plain form picks each lane's row pointer (sp = L without a split: always o)
     const int sp = a.o_split > 0 ? a.o_split : L;
     const int orow = min(qrow, L - 1);
-    T* O = orow < sp ? reinterpret_cast<T*>(a.o) + (((int64_t)s_idx * sp + orow) * a.H + head) * 64
+    // RO: the sequence's first packed row
+    const int64_t orow0 = RO ? (int64_t)reinterpret_cast<const int32_t*>(a.o2)[s_idx] : (int64_t)s_idx * sp;
+    T* O = RO ? reinterpret_cast<T*>(a.o) + ((orow0 + orow) * a.H + head) * 64 : orow < sp ? reinterpret_cast<T*>(a.o) + (((int64_t)s_idx * sp + orow) * a.H + head) * 64
                      : reinterpret_cast<T*>(a.o2) + (((int64_t)s_idx * (L - sp) + (orow - sp)) * a.H + head) * 64;
     // WT: the wave's staging tile, 32 rows x 128 B past the first 4 KB of the ring (the vote flags live there;
     // all reads of the K/V tiles have retired, see above), chunk c of row r at c ^ (r & 7)
@@ -529,7 +543,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
       const int64_t rstride = (int64_t)a.H * 64 * sizeof(T);
       // (split output: the descriptor ends at row sp, which drops the wave's rows of the second part)
       const int sps = __builtin_amdgcn_readfirstlane(sp);
-      const __amdgpu_buffer_rsrc_t ors = rsrc_of(reinterpret_cast<T*>(a.o) + ((int64_t)s_idx * sps * a.H + head) * 64,
+      const __amdgpu_buffer_rsrc_t ors = rsrc_of(reinterpret_cast<T*>(a.o) + ((RO ? orow0 : (int64_t)s_idx * sps) * a.H + head) * 64,
                                                  (uint64_t)(sps - 1) * rstride + 64 * sizeof(T));
       const int row0 = qb * (32 * NW) + wid_s * 32;
       if (row0 < sps) {
@@ -540,7 +554,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
           buffer_store16<kAuxWT>(ors, (uint32_t)((row0 + r) * rstride + c * 16), __builtin_bit_cast(u32x4, w));
         }
       }
-      if (sps < L && row0 + 32 > sps) {
+      if (!RO && sps < L && row0 + 32 > sps) {
         // the wave's rows from sp on, through a descriptor of their own over o2's (sequence, head) columns; rows
         // below sp get an offset past every extent (attn_wt_ok keeps real offsets below 2^31)
         const __amdgpu_buffer_rsrc_t ors2 =
@@ -562,7 +576,8 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
 
 // ---------------------------------------------------------------- fp32 parity kernel
 // RG: two key ranges (AttnArgs::kv_len2), walked one after the other in 32-key tiles by the same loop body
-template <bool RG>
+// RO: ragged output, as attn16_kernel's
+template <bool RG, bool RO = false>
 __global__ __launch_bounds__(64) void attn_f32_kernel(AttnArgs a) {
   const ProbeT probe_t = probe_enter(a.probe);
   __shared__ float Ks[32][65];
@@ -570,14 +585,14 @@ __global__ __launch_bounds__(64) void attn_f32_kernel(AttnArgs a) {
   const int lane = threadIdx.x;
   const int bh = blockIdx.y;
   const int s_idx = bh / a.H, head = bh - s_idx * a.H;
-  const int L = a.L;
-  const int64_t base = (int64_t)bh * L * 64;
+  const int L = RO ? max(0, min(a.L, a.kv_len[s_idx])) : a.L;
+  const int64_t base = (int64_t)bh * a.L * 64;
   const float* Q = reinterpret_cast<const float*>(a.q) + base;
   const float* K = reinterpret_cast<const float*>(a.k) + base;
   const float* V = reinterpret_cast<const float*>(a.v) + base;
   int klen = L;
   if (a.kv_len) klen = min(klen, a.kv_len[s_idx]);
-  if (a.q_len && (int)blockIdx.x * 64 >= a.q_len[s_idx]) {  // dead query block
+  if ((a.q_len && (int)blockIdx.x * 64 >= a.q_len[s_idx]) || (RO && (int)blockIdx.x * 64 >= L)) {  // dead query block
     probe_exit(a.probe, probe_t);
     return;
   }
@@ -631,7 +646,9 @@ __global__ __launch_bounds__(64) void attn_f32_kernel(AttnArgs a) {
   }
   if (qrow < L) {
     const int sp = a.o_split > 0 ? a.o_split : L;  // split output (AttnArgs::o_split)
-    float* O = qrow < sp ? reinterpret_cast<float*>(a.o) + (((int64_t)s_idx * sp + qrow) * a.H + head) * 64
+    float* O = RO ? reinterpret_cast<float*>(a.o) +
+                        (((int64_t)reinterpret_cast<const int32_t*>(a.o2)[s_idx] + qrow) * a.H + head) * 64
+               : qrow < sp ? reinterpret_cast<float*>(a.o) + (((int64_t)s_idx * sp + qrow) * a.H + head) * 64
                          : reinterpret_cast<float*>(a.o2) + (((int64_t)s_idx * (L - sp) + (qrow - sp)) * a.H + head) * 64;
     const float inv = (RG && !(l_run > 0.f)) ? 0.f : 1.f / l_run;  // RG: both ranges empty -> 0
 #pragma unroll
@@ -651,6 +668,15 @@ static void launch16(const AttnArgs& a, hipStream_t st) {
     const char* v = getenv("F5H_ATTN_ROWSUM");
     return v && !strcmp(v, "mfma");
   }();
+  if (a.o_split == kAttnRagged) {  // ragged output: kernels of their own (VALU row sums, as the two-range form)
+    if (a.prescaled && a.store_wt && attn_wt_ok(a))
+      hipLaunchKernelGGL((attn16_kernel<T, true, NW, false, true, false, true>), grid, dim3(64 * NW), 0, st, a);
+    else if (a.prescaled)
+      hipLaunchKernelGGL((attn16_kernel<T, true, NW, false, false, false, true>), grid, dim3(64 * NW), 0, st, a);
+    else
+      hipLaunchKernelGGL((attn16_kernel<T, false, NW, false, false, false, true>), grid, dim3(64 * NW), 0, st, a);
+    return;
+  }
   if (a.kv_len2) {  // two key ranges: kernels of their own (VALU row sums; the engine's form with its store policy)
     if (a.prescaled && a.store_wt && attn_wt_ok(a))
       hipLaunchKernelGGL((attn16_kernel<T, true, NW, false, true, true>), grid, dim3(64 * NW), 0, st, a);
@@ -688,7 +714,11 @@ int attention_store_wt(int compute, const AttnArgs& a, int want) {
 
 hipError_t attention(int compute, const AttnArgs& a0, hipStream_t st) {
   if (a0.S <= 0 || a0.H <= 0 || a0.L <= 0) return hipErrorInvalidValue;
-  if (a0.o_split < 0 || a0.o_split >= a0.L || (a0.o_split > 0 && !a0.o2)) return hipErrorInvalidValue;
+  if (a0.o_split == kAttnRagged) {  // packed output rows: lengths as key and query lengths, one key range
+    if (!a0.o2 || !a0.kv_len || a0.q_len != a0.kv_len || a0.kv_len2) return hipErrorInvalidValue;
+  } else if (a0.o_split < 0 || a0.o_split >= a0.L || (a0.o_split > 0 && !a0.o2)) {
+    return hipErrorInvalidValue;
+  }
   AttnArgs a = a0;
   a.force_safe = g_force_safe;
   if (store_policy_forced() >= 0) a.store_wt = attention_store_wt(compute, a0, store_policy_forced());
@@ -697,7 +727,9 @@ hipError_t attention(int compute, const AttnArgs& a0, hipStream_t st) {
     case F5H_C_FP16: launch16<f16>(a, st); break;
     default: {
       dim3 grid((a.L + 63) / 64, a.S * a.H);
-      if (a.kv_len2)
+      if (a.o_split == kAttnRagged)
+        hipLaunchKernelGGL((attn_f32_kernel<false, true>), grid, dim3(64), 0, st, a);
+      else if (a.kv_len2)
         hipLaunchKernelGGL(attn_f32_kernel<true>, grid, dim3(64), 0, st, a);
       else
         hipLaunchKernelGGL(attn_f32_kernel<false>, grid, dim3(64), 0, st, a);

@@ -18,15 +18,18 @@ namespace f5h {
 // fixed column (c8 = (tid & 7) * 8). Everything the chunks read (bias, row-mask bytes, residual rows)
 // is loaded before any chunk is stored: a load issued after a store waits for it (gfx9 counts stores
 // in vmcnt), and the former per-element bias loads under the row-mask branch waited one by one.
-template <typename TC, int BP, int NT, int CP, int MODE>
-F5H_DEV void conv_epilogue(const ConvArgs& a, const float* Cs, int tid, int s, int n0, int grp, int cg) {
+// RAG (ConvArgs::ragged): the sequence is rows [rb, rb + L) of the packed buffers (L its own length), no row mask
+template <typename TC, int BP, int NT, int CP, int MODE, bool RAG = false>
+F5H_DEV void conv_epilogue(const ConvArgs& a, const float* Cs, int tid, int s, int n0, int grp, int cg, int L,
+                           int64_t rb) {
   constexpr int IT = BP * 8 / NT;
   static_assert(IT * NT == BP * 8 && NT % 8 == 0, "whole chunk passes");
-  const int L = a.L, d = a.d;
+  const int d = a.d;
   const int c8 = (tid & 7) * 8, oc = grp * cg + c8;
   if (c8 >= cg) return;  // (groups narrower than 64 channels)
   const float4 b0 = *reinterpret_cast<const float4*>(a.bias + oc), b1 = *reinterpret_cast<const float4*>(a.bias + oc + 4);
-  const __amdgpu_buffer_rsrc_t rk = rsrc_of(a.rowkeep, a.rowkeep ? (uint64_t)a.S * L : 0);
+  const bool masked = !RAG && a.rowkeep;
+  const __amdgpu_buffer_rsrc_t rk = rsrc_of(a.rowkeep, masked ? (uint64_t)a.S * L : 0);
   uint32_t kb[IT];
   float4 r0[IT], r1[IT];
 #pragma unroll
@@ -34,7 +37,7 @@ F5H_DEV void conv_epilogue(const ConvArgs& a, const float* Cs, int tid, int s, i
     const int pos = min(n0 + (tid >> 3) + it * (NT / 8), L - 1);
     kb[it] = __builtin_amdgcn_raw_buffer_load_b8(rk, (uint32_t)(s * L + pos), 0, 0);
     if constexpr (MODE != 0) {
-      const float* rs = a.resid + ((int64_t)s * L + pos) * d + oc;
+      const float* rs = a.resid + (rb + pos) * d + oc;
       r0[it] = *reinterpret_cast<const float4*>(rs);
       r1[it] = *reinterpret_cast<const float4*>(rs + 4);
     }
@@ -44,7 +47,7 @@ F5H_DEV void conv_epilogue(const ConvArgs& a, const float* Cs, int tid, int s, i
   for (int it = 0; it < IT; ++it) {
     const int row = (tid >> 3) + it * (NT / 8), pos = n0 + row;
     if (pos >= L) continue;
-    const bool keep = !a.rowkeep || kb[it] != 0;
+    const bool keep = !masked || kb[it] != 0;
     const float* c = Cs + row * CP + c8;
     float v[8];
 #pragma unroll
@@ -53,7 +56,7 @@ F5H_DEV void conv_epilogue(const ConvArgs& a, const float* Cs, int tid, int s, i
       v[e] = is16<TC>() ? mish_fast(x) : mish(x);
     }
     if constexpr (MODE == 0) {
-      TC* y = reinterpret_cast<TC*>(a.y) + ((int64_t)s * L + pos) * d + oc;
+      TC* y = reinterpret_cast<TC*>(a.y) + (rb + pos) * d + oc;
       if constexpr (is16<TC>()) {
         typename Op16<TC>::v8 o = {from_f32<TC>(v[0]), from_f32<TC>(v[1]), from_f32<TC>(v[2]), from_f32<TC>(v[3]),
                                    from_f32<TC>(v[4]), from_f32<TC>(v[5]), from_f32<TC>(v[6]), from_f32<TC>(v[7])};
@@ -64,7 +67,7 @@ F5H_DEV void conv_epilogue(const ConvArgs& a, const float* Cs, int tid, int s, i
       }
     } else if constexpr (MODE == 2) {
       if constexpr (is16<TC>()) {
-        TC* y = reinterpret_cast<TC*>(a.y) + ((int64_t)s * a.y_seq_stride + a.y_row_off + pos) * d + oc;
+        TC* y = reinterpret_cast<TC*>(a.y) + (RAG ? rb + pos : (int64_t)s * a.y_seq_stride + a.y_row_off + pos) * d + oc;
         typename Op16<TC>::v8 o = {
             from_f32<TC>(v[0] + r0[it].x), from_f32<TC>(v[1] + r0[it].y), from_f32<TC>(v[2] + r0[it].z),
             from_f32<TC>(v[3] + r0[it].w), from_f32<TC>(v[4] + r1[it].x), from_f32<TC>(v[5] + r1[it].y),
@@ -72,21 +75,34 @@ F5H_DEV void conv_epilogue(const ConvArgs& a, const float* Cs, int tid, int s, i
         *reinterpret_cast<typename Op16<TC>::v8*>(y) = o;
       }
     } else {
-      float* y = reinterpret_cast<float*>(a.y) + ((int64_t)s * a.y_seq_stride + a.y_row_off + pos) * d + oc;
+      float* y = reinterpret_cast<float*>(a.y) + (RAG ? rb + pos : (int64_t)s * a.y_seq_stride + a.y_row_off + pos) * d + oc;
       *reinterpret_cast<float4*>(y) = make_float4(v[0] + r0[it].x, v[1] + r0[it].y, v[2] + r0[it].z, v[3] + r0[it].w);
       *reinterpret_cast<float4*>(y + 4) =
           make_float4(v[4] + r1[it].x, v[5] + r1[it].y, v[6] + r1[it].z, v[7] + r1[it].w);
     }
   }
 }
-template <typename TC, int BP, int NT, int CP>
-F5H_DEV void conv_epilogue_any(const ConvArgs& a, const float* Cs, int tid, int s, int n0, int grp, int cg) {
+template <typename TC, int BP, int NT, int CP, bool RAG = false>
+F5H_DEV void conv_epilogue_any(const ConvArgs& a, const float* Cs, int tid, int s, int n0, int grp, int cg, int L,
+                               int64_t rb) {
   if (a.mode == 0)
-    conv_epilogue<TC, BP, NT, CP, 0>(a, Cs, tid, s, n0, grp, cg);
+    conv_epilogue<TC, BP, NT, CP, 0, RAG>(a, Cs, tid, s, n0, grp, cg, L, rb);
   else if (a.mode == 2)
-    conv_epilogue<TC, BP, NT, CP, 2>(a, Cs, tid, s, n0, grp, cg);
+    conv_epilogue<TC, BP, NT, CP, 2, RAG>(a, Cs, tid, s, n0, grp, cg, L, rb);
   else
-    conv_epilogue<TC, BP, NT, CP, 1>(a, Cs, tid, s, n0, grp, cg);
+    conv_epilogue<TC, BP, NT, CP, 1, RAG>(a, Cs, tid, s, n0, grp, cg, L, rb);
+}
+// the sequence's length and first row: [s*L, (s+1)*L) of the padded buffers, or its segment of the packed ones
+template <bool RAG>
+F5H_DEV void conv_seq(const ConvArgs& a, int s, int& L, int64_t& rb) {
+  if constexpr (RAG) {
+    const int32_t* off = reinterpret_cast<const int32_t*>(a.rowkeep);
+    rb = off[s];
+    L = off[s + 1] - off[s];
+  } else {
+    L = a.L;
+    rb = (int64_t)s * a.L;
+  }
 }
 
 // XCD-aware block -> (position block, group, sequence): the hardware deals workgroups round-robin over the 8
@@ -112,7 +128,7 @@ F5H_DEV void wait_vm() {
 }
 
 // fp32 parity path: NWM x 2 waves; block = 32*NWM positions x 64 output channels, one tap per stage.
-template <typename TC, typename TX, int NWM = 2>
+template <typename TC, typename TX, int NWM = 2, bool RAG = false>
 __global__ __launch_bounds__(128 * NWM, 1) void conv_kernel(ConvArgs a) {
   constexpr int E = elems16<TC>();
   constexpr int CPR = 64 / E;  // 16-byte chunks per 64-channel row (8 bf16 / 16 fp32)
@@ -130,7 +146,12 @@ __global__ __launch_bounds__(128 * NWM, 1) void conv_kernel(ConvArgs a) {
   int pb, grp, s;
   conv_block(pb, grp, s);
   const int n0 = pb * BP;
-  const int L = a.L, d = a.d;
+  const int d = a.d;
+  int L;
+  int64_t rb;
+  conv_seq<RAG>(a, s, L, rb);
+  if (RAG && n0 >= L) return;  // a block past the sequence's end (the grid spans the longest sequence)
+  const bool masked = !RAG && a.rowkeep;
   const TX* X = reinterpret_cast<const TX*>(a.x);
   const int cg = d / 16;  // channels per group (<= 64; padded to 64 in LDS and in the packed weights)
   const TC* Wg = reinterpret_cast<const TC*>(a.w) + (int64_t)grp * 31 * 64 * 64;
@@ -141,8 +162,8 @@ __global__ __launch_bounds__(128 * NWM, 1) void conv_kernel(ConvArgs a) {
   for (int idx = tid; idx < WROWS * CPR; idx += NT) {
     int row = idx / CPR, ch = idx % CPR;
     int q = n0 - 15 + row;
-    bool ok = q >= 0 && q < L && ch * E < cg && (!a.rowkeep || a.rowkeep[(int64_t)s * L + q]);
-    const TX* src = X + ((int64_t)s * L + (ok ? q : 0)) * d + grp * cg + (ok ? ch * E : 0);
+    bool ok = q >= 0 && q < L && ch * E < cg && (!masked || a.rowkeep[rb + q]);
+    const TX* src = X + (rb + (ok ? q : 0)) * d + grp * cg + (ok ? ch * E : 0);
     Xs[row * CPR + swz(row, ch)] = Load16<TC, TX>::ld(src, ok);
   }
   // weight taps stream by LDS-DMA: round r, wave w, lane l -> linear chunk p of the panel;
@@ -233,7 +254,7 @@ __global__ __launch_bounds__(128 * NWM, 1) void conv_kernel(ConvArgs a) {
       for (int r = 0; r < 4; ++r)
         Cs[(wm * 32 + i * 16 + (lane >> 4) * 4 + r) * CP + wn * 32 + j * 16 + (lane & 15)] = acc[i][j][r];
   __syncthreads();
-  conv_epilogue_any<TC, BP, NT, CP>(a, Cs, tid, s, n0, grp, cg);
+  conv_epilogue_any<TC, BP, NT, CP, RAG>(a, Cs, tid, s, n0, grp, cg, L, rb);
 }
 
 // Input-window image: fragment reads take rows t + 16i + (lane & 15) for every tap t, so the
@@ -252,7 +273,7 @@ F5H_DEV int swz_tap(int row, int chunk) {
   return chunk ^ ((r >> 1) ^ ((unsigned)(r - 4) < 8u ? 1 : 0));
 }
 
-template <typename TC, typename TX>
+template <typename TC, typename TX, bool RAG = false>
 __global__ __launch_bounds__(512, 1) void conv16_kernel(ConvArgs a) {
   constexpr int CPR = 8;                  // 16-B chunks per 64-channel row
   constexpr int BP = 256, NT = 512;       // positions per block, threads
@@ -269,7 +290,12 @@ __global__ __launch_bounds__(512, 1) void conv16_kernel(ConvArgs a) {
   int pb, grp, s;
   conv_block(pb, grp, s);
   const int n0 = pb * BP;
-  const int L = a.L, d = a.d;
+  const int d = a.d;
+  int L;
+  int64_t rb;
+  conv_seq<RAG>(a, s, L, rb);
+  if (RAG && n0 >= L) return;  // a block past the sequence's end (the grid spans the longest sequence)
+  const bool masked = !RAG && a.rowkeep;
   const TX* X = reinterpret_cast<const TX*>(a.x);
   const int cg = d / 16;  // channels per group (<= 64; padded to 64 in LDS and in the packed weights)
   const TC* Wg = reinterpret_cast<const TC*>(a.w) + (int64_t)grp * 31 * 64 * 64;
@@ -284,19 +310,19 @@ __global__ __launch_bounds__(512, 1) void conv16_kernel(ConvArgs a) {
     uint4 raw[NIT][8 / EPC];
     uint32_t kb[NIT];
     bool okv[NIT];
-    const __amdgpu_buffer_rsrc_t rk = rsrc_of(a.rowkeep, a.rowkeep ? (uint64_t)a.S * L : 0);
+    const __amdgpu_buffer_rsrc_t rk = rsrc_of(a.rowkeep, masked ? (uint64_t)a.S * L : 0);
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       const int idx = tid + it * NT, row = idx / CPR, ch = idx % CPR;
       const int q = n0 - 15 + row;
       const int qc = min(max(q, 0), L - 1), cc = ch * 8 < cg ? ch * 8 : 0;
       okv[it] = idx < WROWS * CPR && q >= 0 && q < L && ch * 8 < cg;
-      const uint4* src = reinterpret_cast<const uint4*>(X + ((int64_t)s * L + qc) * d + grp * cg + cc);
+      const uint4* src = reinterpret_cast<const uint4*>(X + (rb + qc) * d + grp * cg + cc);
 #pragma unroll
       for (int h = 0; h < 8 / EPC; ++h) raw[it][h] = src[h];  // in range for every idx (clamped row)
       kb[it] = __builtin_amdgcn_raw_buffer_load_b8(rk, (uint32_t)(s * L + qc), 0, 0);
     }
-    if (a.rowkeep) {
+    if (masked) {
 #pragma unroll
       for (int it = 0; it < NIT; ++it) okv[it] = okv[it] && kb[it] != 0;
     }
@@ -443,12 +469,33 @@ __global__ __launch_bounds__(512, 1) void conv16_kernel(ConvArgs a) {
       for (int r = 0; r < 4; ++r)
         Cs[(wm * 64 + i * 16 + (lane >> 4) * 4 + r) * CP + wn * 32 + j * 16 + (lane & 15)] = acc[i][j][r];
   __syncthreads();
-  conv_epilogue_any<TC, BP, NT, CP>(a, Cs, tid, s, n0, grp, cg);
+  conv_epilogue_any<TC, BP, NT, CP, RAG>(a, Cs, tid, s, n0, grp, cg, L, rb);
 }
 
 hipError_t conv_pos(int compute, const ConvArgs& a, hipStream_t st) {
   // groups = 16; d/16 channels per group, padded to the 64-channel tile (d % 128 == 0)
   if (a.d % 128 != 0 || a.d > 1024) return hipErrorInvalidValue;
+  if (a.ragged) {  // packed rows: `rowkeep` carries the segment table
+    if (!a.rowkeep || a.S <= 0 || a.L <= 0) return hipErrorInvalidValue;
+    if (compute == F5H_C_BF16 || compute == F5H_C_FP16) {
+      dim3 grid((a.L + 255) / 256, 16, a.S);
+      if (compute == F5H_C_BF16) {
+        if (a.x_f32)
+          hipLaunchKernelGGL((conv16_kernel<bf16, float, true>), grid, dim3(512), 0, st, a);
+        else
+          hipLaunchKernelGGL((conv16_kernel<bf16, bf16, true>), grid, dim3(512), 0, st, a);
+      } else {
+        if (a.x_f32)
+          hipLaunchKernelGGL((conv16_kernel<f16, float, true>), grid, dim3(512), 0, st, a);
+        else
+          hipLaunchKernelGGL((conv16_kernel<f16, f16, true>), grid, dim3(512), 0, st, a);
+      }
+    } else {
+      dim3 grid((a.L + 63) / 64, 16, a.S);
+      hipLaunchKernelGGL((conv_kernel<float, float, 2, true>), grid, dim3(256), 0, st, a);
+    }
+    return hipGetLastError();
+  }
   if (compute == F5H_C_BF16 || compute == F5H_C_FP16) {
     dim3 grid((a.L + 255) / 256, 16, a.S);
     if (compute == F5H_C_BF16) {

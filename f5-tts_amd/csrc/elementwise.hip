@@ -483,18 +483,29 @@ hipError_t rope_table(int L, float2* out, hipStream_t st) {
 // ---------------------------------------------------------------- text embedding
 // TextEmbedding.forward (dit.py:86-120): tok+1 (filler 0), truncate/pad to N, per-sample
 // valid mask (batched path), fill mask taken BEFORE drop_text, Embedding, + freqs_cis, masked_fill.
+// RAG (TextEmbArgs::seg_off): packed rows, the row's utterance from the segment table; every row is valid, as in the
+// utterance's own call
+template <bool RAG>
 __global__ void text_embed_kernel(TextEmbArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= a.B * a.N) return;
-  const int b = row / a.N, n = row - b * a.N;
-  const bool valid = !a.seq_len || n < a.seq_len[b];
+  const int rows = RAG ? a.N : a.B * a.N;  // (ragged: N counts the packed rows of all utterances)
+  if (row >= rows) return;
+  int b, n;
+  if constexpr (RAG) {
+    b = seg_find(a.seg_off, a.B, row);
+    n = row - a.seg_off[b];
+  } else {
+    b = row / a.N;
+    n = row - b * a.N;
+  }
+  const bool valid = RAG || !a.seq_len || n < a.seq_len[b];
   int tok = n < a.nt ? (int)a.text[(int64_t)b * a.nt + n] + 1 : 0;
   if (!valid) tok = 0;
   const bool fill = tok == 0;
   const bool zero_row = a.mask_padding && a.freqs && fill;  // masked_fill only with extra modeling
   if (a.keep && lane == 0) {
     a.keep[row] = zero_row ? 0 : 1;
-    a.keep[a.B * a.N + row] = zero_row ? 0 : 1;
+    a.keep[rows + row] = zero_row ? 0 : 1;
   }
   for (int c = lane; c < a.td; c += 64) {
     float ec = valid ? a.table[(int64_t)tok * a.td + c] : 0.f;
@@ -511,7 +522,10 @@ __global__ void text_embed_kernel(TextEmbArgs a) {
   }
 }
 hipError_t text_embed(const TextEmbArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL(text_embed_kernel, dim3(nblk((int64_t)a.B * a.N, 4)), dim3(256), 0, st, a);
+  if (a.seg_off)
+    hipLaunchKernelGGL(text_embed_kernel<true>, dim3(nblk((int64_t)a.N, 4)), dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL(text_embed_kernel<false>, dim3(nblk((int64_t)a.B * a.N, 4)), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 
@@ -712,6 +726,55 @@ hipError_t grn(int compute, const float* x, int S, int L, int C, const float* ga
   scratch = nx;
   const int64_t total = (int64_t)S * L * C;
   F5H_OP_DISPATCH(compute, T, hipLaunchKernelGGL(grn_apply_kernel<T>, dim3(nblk(total, 256)), dim3(256), 0, st, x, L, C, scratch, gamma, beta, (T*)out, total););
+  return hipGetLastError();
+}
+
+// GRN over packed rows (kernels.h grn_ragged): the partial sums of sequence s cover its rows [off[s] + 64 z, ..) in
+// grn_sumsq_kernel's order, chunks past its end are exact zeros (as grn's `len` form), and grn_norm_kernel adds them in
+// its fixed order: the sequence's normalisers have the bits of grn on that sequence alone.
+__global__ void grn_sumsq_ragged_kernel(const float* x, const int* off, int S, int C, float* partial) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x, s = blockIdx.y, z = blockIdx.z;
+  if (c >= C) return;
+  const int r0 = off[s], Ls = off[s + 1] - r0;
+  const int n0 = z * 64, n1 = min(Ls, n0 + 64);
+  float acc = 0.f;
+  for (int n = n0; n < n1; ++n) {
+    float v = x[((int64_t)r0 + n) * C + c];
+    acc += v * v;
+  }
+  partial[((int64_t)z * S + s) * C + c] = acc;
+}
+template <typename TO>
+__global__ void grn_apply_ragged_kernel(const float* x, const int* off, int S, int C, const float* nx,
+                                        const float* gamma, const float* beta, TO* out, int64_t total) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  int c = (int)(i % C);
+  int s = seg_find(off, S, (int)(i / C));
+  float v = x[i];
+  out[i] = from_f32<TO>(gamma[c] * (v * nx[(int64_t)s * C + c]) + beta[c] + v);
+}
+hipError_t grn_ragged(int compute, const float* x, const int32_t* off, int S, int R, int Lmax, int C,
+                      const float* gamma, const float* beta, float* scratch, void* out, hipStream_t st) {
+  if (S <= 0 || R <= 0 || Lmax <= 0 || C <= 0 || !off) return hipErrorInvalidValue;
+  const int nz = (int)nblk(Lmax, 64);
+  float* nx = scratch + (size_t)nz * S * C;
+  hipLaunchKernelGGL(grn_sumsq_ragged_kernel, dim3(nblk(C, 256), S, nz), dim3(256), 0, st, x, off, S, C, scratch);
+  hipLaunchKernelGGL(grn_norm_kernel, dim3(S), dim3(1024), 0, st, scratch, nz, S, C, nx);
+  const int64_t total = (int64_t)R * C;
+  F5H_OP_DISPATCH(compute, T, hipLaunchKernelGGL(grn_apply_ragged_kernel<T>, dim3(nblk(total, 256)), dim3(256), 0, st, x, off, S, C, nx, gamma, beta, (T*)out, total););
+  return hipGetLastError();
+}
+__global__ void rowtab_kernel(const int* off, int S, int R, int2* rowtab, int32_t* len) {
+  const int m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m < S && len) len[m] = off[m + 1] - off[m];
+  if (m >= R) return;
+  const int s = seg_find(off, S, m);
+  rowtab[m] = make_int2(s, m - off[s]);
+}
+hipError_t build_rowtab(const int32_t* off, int S, int R, int2* rowtab, int32_t* len, hipStream_t st) {
+  if (S <= 0 || R < S || !off || !rowtab) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rowtab_kernel, dim3(nblk(R, 256)), dim3(256), 0, st, off, S, R, rowtab, len);
   return hipGetLastError();
 }
 

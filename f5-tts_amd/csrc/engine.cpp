@@ -89,13 +89,16 @@ struct GraphKey {
   // MMDiT single-branch forward (kind 2): the captured step reads the text stream's start from the conditional or the
   // dropped-text embedding, so drop_text is part of the key (DiT / UNetT: the drop flags act in the prologue only)
   int drop_text;
+  // ragged sampling (f5h_sample_ragged; 0 otherwise): utterances and longest utterance. With N = the packed rows R these
+  // fix the launch geometry; the lengths themselves live in the workspace's segment tables, not in the key
+  int rag_B, rag_L;
   uint64_t kernel_epoch;  // bumped whenever a forced GEMM config changes
   uint32_t cfg_bits;
   bool operator==(const GraphKey& o) const {
     return ws == o.ws && kind == o.kind && B == o.B && N == o.N && nt == o.nt && nfe == o.nfe && kernel_epoch == o.kernel_epoch &&
            use_cfg == o.use_cfg && batch_mask == o.batch_mask && probe == o.probe && cfg_bits == o.cfg_bits &&
            split == o.split && pad_skip == o.pad_skip && chain == o.chain && lnfold == o.lnfold && store == o.store &&
-           method == o.method && drop_text == o.drop_text;
+           method == o.method && drop_text == o.drop_text && rag_B == o.rag_B && rag_L == o.rag_L;
   }
 };
 
@@ -671,12 +674,19 @@ struct Bufs {
   uint8_t* in_mask;
   int64_t* in_text;
   int32_t* in_dur;
+  // ragged sampling (null otherwise): the segment table of the 2B sequences, off[2B + 1] (the conditional branch's B
+  // utterances, then the unconditional branch's; off[B] = R, off[2B] = 2R), their lengths [2B] and the per-row
+  // (sequence, position) table [2R] of the QKV epilogue
+  int32_t *rg_off, *rg_len;
+  int2* rg_tab;
 };
 
 // nfe: table rows. method / steps: the multi-stage solvers' extra buffers (none for Euler, whose layout is unchanged)
 // nt: text tokens (MMDiT only: its text stream's buffers; the other backbones' layouts do not depend on it)
+// rgB / rgL (ragged sampling: utterances and the longest one; the call then passes B = 1 and N = R, the packed rows of
+// one CFG branch): every [S*N, .] buffer holds the 2R packed rows; q / k / v are padded panels [2 rgB, heads, rgL, 64]
 static void layout(const f5h_engine* e, WS& ws, Bufs& b, int B, int N, int nfe, int use_cfg, int method = 0,
-                   int steps = 0, int nt = 0) {
+                   int steps = 0, int nt = 0, int rgB = 0, int rgL = 0) {
   const f5h_arch& a = e->a;
   const int d = a.dim, td = a.text_dim, S = use_cfg ? 2 * B : B;
   const bool mm = a.backbone == F5H_MMDIT;
@@ -695,7 +705,8 @@ static void layout(const f5h_engine* e, WS& ws, Bufs& b, int B, int N, int nfe, 
     b.dwln = ws.take<char>((size_t)2 * B * N * td * es);
     b.pw1o = ws.take<float>((size_t)2 * B * N * 2 * td);
     b.grno = ws.take<char>((size_t)2 * B * N * 2 * td * es);
-    b.grn_scr = ws.take<float>((size_t)((N + 63) / 64 + 1) * 2 * B * 2 * td);
+    b.grn_scr = rgB ? ws.take<float>((size_t)((rgL + 63) / 64 + 1) * 2 * rgB * 2 * td)
+                    : ws.take<float>((size_t)((N + 63) / 64 + 1) * 2 * B * 2 * td);
   } else {
     b.dwln = b.grno = nullptr;
     b.pw1o = b.grn_scr = nullptr;
@@ -707,9 +718,10 @@ static void layout(const f5h_engine* e, WS& ws, Bufs& b, int B, int N, int nfe, 
   b.c1 = ws.take<char>((size_t)S * N * d * es);
   b.h = adaln_bb(a) ? ws.take<float>(rows * d) : nullptr;  // DiT / MMDiT (audio) residual stream
   b.aop = ws.take<char>(rows * d * es);
-  b.q = ws.take<char>(jrows * inner * es);
-  b.k = ws.take<char>(jrows * inner * es);
-  b.v = ws.take<char>(jrows * inner * es);
+  const size_t qrows = rgB ? (size_t)(use_cfg ? 2 : 1) * rgB * rgL : jrows;
+  b.q = ws.take<char>(qrows * inner * es);
+  b.k = ws.take<char>(qrows * inner * es);
+  b.v = ws.take<char>(qrows * inner * es);
   b.o = ws.take<char>(rows * inner * es);
   b.f = ws.take<char>(rows * a.ff_dim * es);
   b.p = ws.take<float>(rows * e->proj_out.Npad);  // proj_out rows padded to the GEMM tile width
@@ -754,6 +766,9 @@ static void layout(const f5h_engine* e, WS& ws, Bufs& b, int B, int N, int nfe, 
   b.ckeep = mm ? ws.take<uint8_t>(crows) : nullptr;
   b.tlen = mm ? ws.take<int32_t>(S) : nullptr;
   b.rowkeep_n = a.backbone != F5H_UNETT ? nullptr : a.conv_layers > 0 ? ws.take<uint8_t>((size_t)S * N) : b.keepfill;
+  b.rg_off = rgB ? ws.take<int32_t>((size_t)2 * rgB + 1) : nullptr;
+  b.rg_len = rgB ? ws.take<int32_t>((size_t)2 * rgB) : nullptr;
+  b.rg_tab = rgB ? ws.take<int2>((size_t)2 * N) : nullptr;
 }
 
 // ---------------------------------------------------------------- probe
@@ -815,6 +830,10 @@ struct Ctx {
   int lnfold;  // this call runs the LayerNorm fold (engine switch, shape; never beside the chain)
   int store;   // the engine's store policy at the start of the call
   double* hp;  // host milliseconds of the call by phase (kHostPhases, f5h_last_call_host_ms), or null
+  // ragged sampling (f5h_sample_ragged; rag_B = 0 otherwise): rag_B utterances of at most rag_L frames as packed rows.
+  // The row-local launches see B = 1, N = L = R (one "sequence" per CFG branch); the four kernels that reach across
+  // rows take the segment tables (Bufs rg_*), which the call uploads before the prologue
+  int rag_B, rag_L;
 };
 // Host time of an f5h_sample call by phase (f5h_last_call_host_ms): a call that blocks the host shows where.
 enum { HP_TOTAL = 0, HP_PROLOGUE, HP_LOCK, HP_REAP, HP_CAPTURE, HP_INSTANTIATE, HP_LAUNCH, HP_FINAL, kHostPhases };
@@ -853,7 +872,8 @@ static int prologue(Ctx& c, const float* t_host, int nt_vals, const float* cond,
   Bufs& b = c.b;
   hipStream_t st = c.st;
   const bool mm = a.backbone == F5H_MMDIT;
-  KCK(rope_table(mm ? std::max(c.N, c.nt) : c.L, b.rope, st));
+  KCK(rope_table(c.rag_B ? c.rag_L : mm ? std::max(c.N, c.nt) : c.L, b.rope, st));
+  if (c.rag_B) KCK(build_rowtab(b.rg_off, 2 * c.rag_B, 2 * c.N, b.rg_tab, b.rg_len, st));
   if (mm) KCK(build_textkeep(text, c.B, c.S, c.nt, b.ckeep, st));  // c_mask (mmdit.py:232), both branches
   const int off = adaln_bb(a) ? 0 : 1;
   if (c.batch_mask) {
@@ -915,10 +935,11 @@ static int prologue(Ctx& c, const float* t_host, int nt_vals, const float* cond,
   } else if (!text_cached) {
     TextEmbArgs t{};
     t.text = text;
-    t.B = c.B;
+    t.B = c.rag_B ? c.rag_B : c.B;
     t.nt = c.nt;
     t.N = c.N;
     t.td = td;
+    t.seg_off = b.rg_off;  // ragged: utterance b's tokens, then filler, on its own packed rows (null otherwise)
     t.seq_len = (a.backbone == F5H_DIT && c.batch_mask) ? duration : nullptr;
     t.table = e->text_table;
     t.freqs = a.conv_layers > 0 ? e->freqs : nullptr;
@@ -933,10 +954,16 @@ static int prologue(Ctx& c, const float* t_host, int nt_vals, const float* cond,
     const int32_t* tl = c.isolate ? duration : nullptr;
     for (int i = 0; i < a.conv_layers; ++i) {
       CNX& x = e->cnx[i];
-      KCK(dwconv_ln(bf, b.te, S2, c.N, td, x.dw_w, x.dw_b, x.ln_w, x.ln_b, b.dwln, st, tl, c.B));
+      if (c.rag_B)  // the 2 rag_B sequences of both branches on the 2R packed rows
+        KCK(dwconv_ln_ragged(bf, b.te, b.rg_off, 2 * c.rag_B, R2, td, x.dw_w, x.dw_b, x.ln_w, x.ln_b, b.dwln, st));
+      else
+        KCK(dwconv_ln(bf, b.te, S2, c.N, td, x.dw_w, x.dw_b, x.ln_w, x.ln_b, b.dwln, st, tl, c.B));
       GemmArgs g = gargs(b.dwln, td, x.pw1, R2, b.pw1o, 2 * td);
       KCK(gemm(bf, EPI_GELU_ERF, g, st));
-      KCK(grn(bf, b.pw1o, S2, c.N, 2 * td, x.gamma, x.beta, b.grn_scr, b.grno, st, tl, c.B));
+      if (c.rag_B)
+        KCK(grn_ragged(bf, b.pw1o, b.rg_off, 2 * c.rag_B, R2, c.rag_L, 2 * td, x.gamma, x.beta, b.grn_scr, b.grno, st));
+      else
+        KCK(grn(bf, b.pw1o, S2, c.N, 2 * td, x.gamma, x.beta, b.grn_scr, b.grno, st, tl, c.B));
       g = gargs(b.grno, 2 * td, x.pw2, R2, b.te, td);
       g.rowkeep = a.text_mask_padding ? b.keepfill : nullptr;
       KCK(gemm(bf, EPI_RESID_FILL, g, st));
@@ -1045,6 +1072,12 @@ static int backbone_part(Ctx& c, int s0, int ns, hipStream_t st) {
     cv.bias = e->conv_b[0];
     cv.mode = 0;
     cv.y = op(b.c1, no, d);
+    if (c.rag_B) {  // packed rows: the part's sequences by the segment table (always the whole packed batch, s0 == 0)
+      cv.ragged = 1;
+      cv.S = ns * c.rag_B;
+      cv.L = c.rag_L;
+      cv.rowkeep = reinterpret_cast<const uint8_t*>(b.rg_off);
+    }
     {
       ProbeScope ps(e, KC_CONV, st, &c.site);
       KCK(conv_pos(bf, cv, st));
@@ -1087,6 +1120,11 @@ static int backbone_part(Ctx& c, int s0, int ns, hipStream_t st) {
     g.q_norm_w = Lq.q_norm_w;  // qk_norm (null without it): RMSNorm of every q / k head ahead of RoPE
     g.k_norm_w = Lq.k_norm_w;
     g.qk_norm_eps = 1e-6f;     // modules.py:406-407
+    if (c.rag_B) {  // packed rows into padded panels [sequences, H, rag_L, 64] (kernels.h qkv_rowtab)
+      g.add = reinterpret_cast<const float*>(b.rg_tab);
+      g.seq_len = c.rag_L;
+      g.qkv_dst_len = c.rag_L;
+    }
     return g;
   };
   // In-launch phase chain (chain.hip): a layer's out-proj .. FFN2 plus the next layer's LayerNorm + QKV (or
@@ -1206,6 +1244,13 @@ static int backbone_part(Ctx& c, int s0, int ns, hipStream_t st) {
       // pad query rows' outputs are zeroed after to_out (modules.py:551-553): their blocks are skipped
       at.q_len = (c.batch_mask && e->pad_skip) ? b.kvlen + s0 : nullptr;
       at.prescaled = 1;
+      if (c.rag_B) {  // the sequences' own lengths as key and query lengths; O back to the packed rows
+        at.S = ns * c.rag_B;
+        at.L = c.rag_L;
+        at.kv_len = at.q_len = b.rg_len;
+        at.o_split = kAttnRagged;
+        at.o2 = b.rg_off;
+      }
       at.store_wt = attention_store_wt(bf, at, store_want(c.store, KC_ATTN));
       count_store(at.store_wt);
       ProbeScope ps(e, KC_ATTN, st, &c.site, &at.probe);
@@ -1867,12 +1912,12 @@ size_t f5h_workspace_size(const f5h_engine* e, int32_t B, int32_t N, int32_t nt,
 static int check_ws(f5h_engine* e, int B, int N, int nfe, int use_cfg, void* w, size_t bytes, Ctx& c, int method = 0,
                     int steps = 0) {
   WS ws;
-  layout(e, ws, c.b, B, N, nfe + 1, use_cfg, method, steps, c.nt);
+  layout(e, ws, c.b, B, N, nfe + 1, use_cfg, method, steps, c.nt, c.rag_B, c.rag_L);
   if (bytes < ws.off)
     return fail(F5H_ENOMEM, "workspace too small: need " + std::to_string(ws.off) + " have " + std::to_string(bytes));
   ws.off = 0;
   ws.base = reinterpret_cast<char*>(w);
-  layout(e, ws, c.b, B, N, nfe + 1, use_cfg, method, steps, c.nt);
+  layout(e, ws, c.b, B, N, nfe + 1, use_cfg, method, steps, c.nt, c.rag_B, c.rag_L);
   return 0;
 }
 // MMDiT calls (f5h_sample / f5h_forward): what the joint attention cannot serve
@@ -1910,6 +1955,8 @@ static GraphKey prologue_key(const Ctx& c, const void* ws) {
   key.lnfold = c.lnfold;
   key.store = c.store;
   key.method = c.method;
+  key.rag_B = c.rag_B;
+  key.rag_L = c.rag_L;
   key.kernel_epoch = g_kernel_epoch.load();
   return key;
 }
@@ -1977,8 +2024,14 @@ int f5h_debug_ode_eval_times(int32_t method, int32_t compute, const float* t_gri
   return 0;
 }
 
+// A ragged call (f5h_sample_ragged): B utterances of `dur` (host) frames, at most Lmax, as the packed rows of `a`
+// (a->B = 1, a->N = R)
+struct RagCall {
+  int B, Lmax;
+  const int32_t* dur;
+};
 static int sample_impl(f5h_engine* e, void* stream, const f5h_sample_args* a, int method, void* workspace,
-                       size_t workspace_bytes);
+                       size_t workspace_bytes, const RagCall* rg = nullptr);
 int f5h_sample(f5h_engine* e, void* stream, const f5h_sample_args* a, void* workspace, size_t workspace_bytes) {
   return sample_impl(e, stream, a, F5H_EULER, workspace, workspace_bytes);
 }
@@ -1988,9 +2041,67 @@ int f5h_sample_ode(f5h_engine* e, void* stream, const f5h_sample_args* a, int32_
   return sample_impl(e, stream, a, method, workspace, workspace_bytes);
 }
 
+static int check_ragged_call(const f5h_engine* e, int B, int64_t R, int Lmax, const int32_t* dur) {
+  if (!e) return fail(F5H_EINVAL, "null engine");
+  if (e->a.backbone != F5H_DIT)
+    return fail(F5H_EINVAL, "ragged sampling serves the DiT backbone only (UNetT's time-token row and MMDiT's joint "
+                            "sequence are not packed)");
+  if (e->a.text_average_upsampling)
+    return fail(F5H_EINVAL, "ragged sampling does not serve text_embedding_average_upsampling");
+  if (B <= 0 || R <= 0 || Lmax <= 0) return fail(F5H_EINVAL, "ragged sampling: bad B / R / Lmax");
+  // 2R rows index 32-bit buffer descriptors and the division-free row arithmetic of the GEMM epilogues (2^24 rows)
+  if (2 * R >= (int64_t)1 << 24) return fail(F5H_EINVAL, "ragged sampling: 2 R must stay below 2^24 rows");
+  if (dur) {
+    int64_t sum = 0;
+    for (int b = 0; b < B; ++b) {
+      if (dur[b] < 1) return fail(F5H_EINVAL, "ragged sampling: duration[" + std::to_string(b) + "] is below 1");
+      if (dur[b] > Lmax)
+        return fail(F5H_EINVAL, "ragged sampling: duration[" + std::to_string(b) + "] exceeds Lmax");
+      sum += dur[b];
+    }
+    if (sum != R) return fail(F5H_EINVAL, "ragged sampling: the durations add up to " + std::to_string(sum) + ", not R");
+  }
+  return 0;
+}
+size_t f5h_workspace_size_ragged(const f5h_engine* e, int32_t B, int64_t R, int32_t Lmax, int32_t nt, int32_t steps,
+                                 int32_t use_cfg, int32_t method) {
+  (void)nt;
+  if (!e || steps <= 0 || method < 0 || method >= kOdeMethods || R > INT32_MAX) return 0;
+  if (check_ragged_call(e, B, R, Lmax, nullptr)) return 0;
+  WS ws;
+  Bufs b;
+  layout(e, ws, b, 1, (int)R, steps * ode_tableau(method).stages + 1, use_cfg, method, steps, 0, B, Lmax);
+  return ws.off;
+}
+int f5h_sample_ragged(f5h_engine* e, void* stream, const f5h_ragged_args* r, int32_t method, void* workspace,
+                      size_t workspace_bytes) {
+  if (!e || !r) return fail(F5H_EINVAL, "null engine/args");
+  if (method < 0 || method >= kOdeMethods) return fail(F5H_EINVAL, "ode method must be 0 (euler), 1 (midpoint) or 2 (rk4)");
+  if (!r->duration) return fail(F5H_EINVAL, "null tensor argument");
+  if (r->R > INT32_MAX) return fail(F5H_EINVAL, "ragged sampling: R too large");
+  RC(check_ragged_call(e, r->B, r->R, r->Lmax, r->duration));
+  f5h_sample_args a{};
+  a.B = 1;
+  a.N = (int32_t)r->R;
+  a.nt = r->nt;
+  a.nfe = r->nfe;
+  a.cond = r->cond;
+  a.cond_mask = r->cond_mask;
+  a.text = r->text;
+  a.duration = nullptr;
+  a.y0 = r->y0;
+  a.t_grid = r->t_grid;
+  a.cfg_strength = r->cfg_strength;
+  a.use_batch_mask = 0;
+  a.out = r->out;
+  a.trajectory = r->trajectory;
+  const RagCall rg{r->B, r->Lmax, r->duration};
+  return sample_impl(e, stream, &a, method, workspace, workspace_bytes, &rg);
+}
+
 // method F5H_EULER: the Euler path exactly as before the other solvers existed (same launches, same layout).
 static int sample_impl(f5h_engine* e, void* stream, const f5h_sample_args* a, int method, void* workspace,
-                       size_t workspace_bytes) {
+                       size_t workspace_bytes, const RagCall* rg) {
   if (!e || !a) return fail(F5H_EINVAL, "null engine/args");
   if (a->B <= 0 || a->N <= 0 || a->nt < 0 || a->nfe <= 0 || a->nfe > 512)
     return fail(F5H_EINVAL, "bad B/N/nt/nfe");
@@ -1999,9 +2110,10 @@ static int sample_impl(f5h_engine* e, void* stream, const f5h_sample_args* a, in
     return fail(F5H_EINVAL, std::to_string(a->nfe) + " steps x " + std::to_string(stages) + " stages = " +
                                 std::to_string(a->nfe * stages) +
                                 " backbone evaluations exceed the 512 rows of the per-call time tables");
-  if (!a->cond || !a->cond_mask || !a->duration || !a->y0 || !a->t_grid || !a->out || (a->nt > 0 && !a->text))
+  if (!a->cond || !a->cond_mask || (!a->duration && !rg) || !a->y0 || !a->t_grid || !a->out || (a->nt > 0 && !a->text))
     return fail(F5H_EINVAL, "null tensor argument");
-  if (e->a.backbone == F5H_DIT && a->N > 8192) return fail(F5H_EINVAL, "N exceeds the text position table (8192)");
+  if (e->a.backbone == F5H_DIT && (rg ? rg->Lmax : a->N) > 8192)
+    return fail(F5H_EINVAL, "N exceeds the text position table (8192)");
   HIPCK(hipSetDevice(e->dev));
   UseNote used{e->uses, reinterpret_cast<hipStream_t>(stream)};  // on every return: the engine's release waits for it
   Ctx c{};
@@ -2019,12 +2131,23 @@ static int sample_impl(f5h_engine* e, void* stream, const f5h_sample_args* a, in
   if (a->use_batch_mask < 0 || a->use_batch_mask > 2) return fail(F5H_EINVAL, "use_batch_mask must be 0, 1 or 2");
   c.batch_mask = a->use_batch_mask ? 1 : 0;
   c.isolate = a->use_batch_mask == 2 ? 1 : 0;
+  c.rag_B = rg ? rg->B : 0;
+  c.rag_L = rg ? rg->Lmax : 0;
   RC(check_mmdit_call(e, c.nt, c.batch_mask, c.isolate));
   RC(check_ws(e, c.B, c.N, c.nfe, c.use_cfg, workspace, workspace_bytes, c, method, c.steps));
   RC(chain_fault_check(e, c.st));
   ChainTicket ticket;  // (declared after `used`: its event is recorded first, both after every launch of the call)
-  c.chain = chain_for_call(e, c, ticket);
-  c.lnfold = e->lnfold && !c.chain && ((e->lnf_ok && !c.batch_mask) || e->rmsf_ok);
+  // ragged: no chain and no fold, as for every masked batch (each utterance then has the bits of its own unfolded call)
+  c.chain = rg ? 0 : chain_for_call(e, c, ticket);
+  c.lnfold = !rg && e->lnfold && !c.chain && ((e->lnf_ok && !c.batch_mask) || e->rmsf_ok);
+  if (rg) {
+    // the segment table of both branches' sequences, from the host lengths (by kernel argument, stream-ordered); the
+    // prologue derives the lengths and the per-row table from it on the device
+    std::vector<int32_t> off((size_t)2 * rg->B + 1);
+    off[0] = 0;
+    for (int s = 0; s < 2 * rg->B; ++s) off[s + 1] = off[s] + rg->dur[s % rg->B];
+    HIPCK(seg_upload(off.data(), (int64_t)off.size(), c.b.rg_off, c.st));
+  }
   c.store = e->store_policy;
   double hp[kHostPhases] = {};
   c.hp = hp;
@@ -2047,7 +2170,8 @@ static int sample_impl(f5h_engine* e, void* stream, const f5h_sample_args* a, in
     HIPCK(grid_upload(a->t_grid, c.steps + 1, c.b.sgrid, c.st));
   }
   const GraphKey pkey = prologue_key(c, workspace);
-  if (pro_graph && e->graph_mode && c.nt <= c.N && prologue_repeats(e, pkey))
+  // (a ragged call's prologue runs eagerly: its text is [B, nt], which the staging slots of a B = 1 layout do not hold)
+  if (pro_graph && e->graph_mode && !rg && c.nt <= c.N && prologue_repeats(e, pkey))
     RC(prologue_graph(c, a, pkey));
   else
     RC(prologue(c, t_rows, c.nfe, a->cond, a->cond_mask, a->text, a->duration));
@@ -2166,7 +2290,10 @@ static int run_steps(Ctx& c, const f5h_sample_args* a, const void* ws) {
   key.use_cfg = c.use_cfg;
   key.batch_mask = c.batch_mask + c.isolate;
   key.probe = e->probe_class;
-  const bool split = e->split_cfg == 1;  // auto (2): one packed chain
+  // auto (2): one packed chain. Ragged: always one chain (the segment tables address the packed batch as a whole)
+  const bool split = e->split_cfg == 1 && !c.rag_B;
+  key.rag_B = c.rag_B;
+  key.rag_L = c.rag_L;
   key.split = split;
   key.pad_skip = e->pad_skip;
   key.chain = c.chain;
@@ -2718,11 +2845,6 @@ int f5h_op_attention_ranges(void* stream, int32_t compute, int32_t S, int32_t H,
                            workspace_bytes, 0, nullptr, kv_start2, kv_len2);
 }
 
-// ---- op-level entry points of the conv / norm / GEMM-epilogue kernels (tests/test_gpu_ops.py). Each validates
-// its shapes on the host (F5H_EINVAL, nothing enqueued), stages the operand-dtype buffers the kernel's contract
-// asks for in the caller's workspace (f32_to_op / op_to_f32), calls the production launcher unchanged and
-// returns fp32. A buffer the kernel writes in the operand dtype starts as the rounded copy of the caller's
-// fp32 buffer, so elements the kernel leaves alone come back as they went in.
 static bool op_compute_ok(int32_t compute) { return compute >= F5H_FP32 && compute <= F5H_FP16; }
 // caller workspace as a bump allocator: null when it does not fit (fits() then fails the call)
 struct OpWs {
@@ -2736,6 +2858,138 @@ struct OpWs {
   do {                                                                                            \
     if (!(w).fits()) return fail(F5H_ENOMEM, std::string("workspace too small for ") + (what));  \
   } while (0)
+
+// A host segment table off[S + 1] of an op hook: off[0] = 0, every length in [1, Lmax], off[S] = R
+static int op_seg_check(const char* what, const int32_t* off, int S, int64_t R, int Lmax) {
+  if (!off || S <= 0 || R <= 0 || Lmax <= 0) return fail(F5H_EINVAL, std::string(what) + ": bad segment table");
+  if (off[0] != 0 || off[S] != R) return fail(F5H_EINVAL, std::string(what) + ": seg_off must run from 0 to R");
+  for (int s = 0; s < S; ++s)
+    if (off[s + 1] - off[s] < 1 || off[s + 1] - off[s] > Lmax)
+      return fail(F5H_EINVAL, std::string(what) + ": segment " + std::to_string(s) + " is empty or longer than Lmax");
+  return 0;
+}
+
+int f5h_op_attention_ragged(void* stream, int32_t compute, int32_t S, int32_t H, int32_t Lmax, int32_t R,
+                            const int32_t* seg_off, const float* Q, const float* K, const float* V,
+                            int32_t q_prescaled, float* O, void* workspace, size_t workspace_bytes) {
+  if (!op_compute_ok(compute)) return fail(F5H_EINVAL, "bad compute mode");
+  if (S <= 0 || H <= 0 || !Q || !K || !V || !O) return fail(F5H_EINVAL, "op_attention_ragged: bad shape or null tensor");
+  RC(op_seg_check("op_attention_ragged", seg_off, S, R, Lmax));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t n = (int64_t)S * H * Lmax * 64, no = (int64_t)R * H * 64;
+  const size_t es = compute ? 2 : 4;
+  OpWs ws(workspace, workspace_bytes);
+  int32_t* off = reinterpret_cast<int32_t*>(ws.take((size_t)(S + 1) * 4));
+  int32_t* len = reinterpret_cast<int32_t*>(ws.take((size_t)S * 4));
+  int2* tab = reinterpret_cast<int2*>(ws.take((size_t)R * 8));
+  void* q = compute ? ws.take((size_t)n * es) : nullptr;
+  void* k = compute ? ws.take((size_t)n * es) : nullptr;
+  void* v = compute ? ws.take((size_t)n * es) : nullptr;
+  void* o = compute ? ws.take((size_t)no * es) : nullptr;
+  OPWS_CHECK(ws, "op_attention_ragged");
+  HIPCK(seg_upload(seg_off, S + 1, off, st));
+  HIPCK(build_rowtab(off, S, R, tab, len, st));
+  AttnArgs at{};
+  at.S = S;
+  at.H = H;
+  at.L = Lmax;
+  at.kv_len = at.q_len = len;
+  at.prescaled = q_prescaled ? 1 : 0;
+  at.o_split = kAttnRagged;
+  at.o2 = off;
+  at.q = Q;
+  at.k = K;
+  at.v = V;
+  at.o = O;
+  if (compute) {
+    HIPCK(f32_to_op(compute, Q, n, q, st));
+    HIPCK(f32_to_op(compute, K, n, k, st));
+    HIPCK(f32_to_op(compute, V, n, v, st));
+    HIPCK(f32_to_op(compute, O, no, o, st));
+    at.q = q;
+    at.k = k;
+    at.v = v;
+    at.o = o;
+  }
+  HIPCK(attention(compute, at, st));
+  if (compute) HIPCK(op_to_f32(compute, o, no, O, st));
+  return 0;
+}
+
+int f5h_op_conv_pos_ragged(void* stream, int32_t compute, int32_t S, int32_t Lmax, int32_t R, int32_t d,
+                           const int32_t* seg_off, const float* x, const float* w, const float* bias, int32_t mode,
+                           const float* resid, int32_t x_as_f32, float* y, void* workspace, size_t workspace_bytes) {
+  if (!op_compute_ok(compute)) return fail(F5H_EINVAL, "bad compute mode");
+  if (d <= 0 || d % 128 || d > 1024) return fail(F5H_EINVAL, "op_conv_pos_ragged needs d % 128 == 0 and d <= 1024");
+  if (mode < 0 || mode > 2 || (mode == 2 && !compute)) return fail(F5H_EINVAL, "op_conv_pos_ragged: bad mode");
+  if (!x || !w || !bias || !y || (mode != 0 && !resid)) return fail(F5H_EINVAL, "op_conv_pos_ragged: null tensor");
+  RC(op_seg_check("op_conv_pos_ragged", seg_off, S, R, Lmax));
+  if ((int64_t)R * d >= (int64_t)1 << 31) return fail(F5H_EINVAL, "op_conv_pos_ragged: R * d must stay below 2^31");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const size_t es = compute ? 2 : 4;
+  const int64_t nx = (int64_t)R * d;
+  OpWs ws(workspace, workspace_bytes);
+  void* wp = ws.take(kConvPackElems * es);
+  int32_t* off = reinterpret_cast<int32_t*>(ws.take((size_t)(S + 1) * 4));
+  void* xop = (compute && !x_as_f32) ? ws.take((size_t)nx * es) : nullptr;
+  const bool y16 = compute && mode != 1;
+  void* yop = y16 ? ws.take((size_t)nx * es) : nullptr;
+  OPWS_CHECK(ws, "op_conv_pos_ragged");
+  HIPCK(hipMemsetAsync(wp, 0, kConvPackElems * es, st));
+  RC(pack_conv_weight(w, F5H_DT_F32, d, wp, compute, st));
+  HIPCK(seg_upload(seg_off, S + 1, off, st));
+  ConvArgs cv{};
+  cv.S = S;
+  cv.L = Lmax;
+  cv.d = d;
+  cv.ragged = 1;
+  cv.rowkeep = reinterpret_cast<const uint8_t*>(off);
+  cv.x = x;
+  cv.x_f32 = 1;
+  if (xop) {
+    HIPCK(f32_to_op(compute, x, nx, xop, st));
+    cv.x = xop;
+    cv.x_f32 = 0;
+  }
+  cv.w = wp;
+  cv.bias = bias;
+  cv.mode = mode;
+  cv.y = y;
+  if (yop) {
+    HIPCK(f32_to_op(compute, y, nx, yop, st));
+    cv.y = yop;
+  }
+  cv.resid = resid;
+  HIPCK(conv_pos(compute, cv, st));
+  if (yop) HIPCK(op_to_f32(compute, yop, nx, y, st));
+  return 0;
+}
+
+int f5h_op_grn_ragged(void* stream, int32_t compute, int32_t S, int32_t Lmax, int32_t R, int32_t C,
+                      const int32_t* seg_off, const float* x, const float* gamma, const float* beta, float* out,
+                      void* workspace, size_t workspace_bytes) {
+  if (!op_compute_ok(compute)) return fail(F5H_EINVAL, "bad compute mode");
+  if (C <= 0 || !x || !gamma || !beta || !out) return fail(F5H_EINVAL, "op_grn_ragged: bad shape or null tensor");
+  RC(op_seg_check("op_grn_ragged", seg_off, S, R, Lmax));
+  if (S > 65535 || (Lmax + 63) / 64 > 65535) return fail(F5H_EINVAL, "op_grn_ragged: S and Lmax / 64 are grid dimensions");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t n = (int64_t)R * C;
+  OpWs ws(workspace, workspace_bytes);
+  int32_t* off = reinterpret_cast<int32_t*>(ws.take((size_t)(S + 1) * 4));
+  float* scratch = reinterpret_cast<float*>(ws.take(((size_t)(Lmax + 63) / 64 + 1) * S * C * sizeof(float)));
+  void* oop = compute ? ws.take((size_t)n * 2) : nullptr;
+  OPWS_CHECK(ws, "op_grn_ragged");
+  HIPCK(seg_upload(seg_off, S + 1, off, st));
+  HIPCK(grn_ragged(compute, x, off, S, R, Lmax, C, gamma, beta, scratch, oop ? oop : (void*)out, st));
+  if (oop) HIPCK(op_to_f32(compute, oop, n, out, st));
+  return 0;
+}
+
+// ---- op-level entry points of the conv / norm / GEMM-epilogue kernels (tests/test_gpu_ops.py). Each validates
+// its shapes on the host (F5H_EINVAL, nothing enqueued), stages the operand-dtype buffers the kernel's contract
+// asks for in the caller's workspace (f32_to_op / op_to_f32), calls the production launcher unchanged and
+// returns fp32. A buffer the kernel writes in the operand dtype starts as the rounded copy of the caller's
+// fp32 buffer, so elements the kernel leaves alone come back as they went in.
 
 int f5h_op_conv_pos(void* stream, int32_t compute, int32_t S, int32_t L, int32_t d, const float* x, const float* w,
                     const float* bias, const uint8_t* rowkeep, int32_t mode, const float* resid, int32_t x_as_f32,
@@ -2905,9 +3159,16 @@ int f5h_op_gemm_epi(void* stream, const f5h_op_gemm_args* a, void* workspace, si
     return fail(F5H_EINVAL, "op_gemm_epi: add / dual_rows go with EPI_INPROJ");
   }
   int inner = 0;
+  const bool rq = a->seg_off != nullptr;  // ragged QKV rows (packed sequences into padded panels)
+  if (rq) {
+    if (epi != EPI_QKV) return fail(F5H_EINVAL, "op_gemm_epi: seg_off goes with EPI_QKV");
+    if (a->qkv_dst_len <= 0 || a->seq_len != a->qkv_dst_len || a->ln_part_in)
+      return fail(F5H_EINVAL, "op_gemm_epi: ragged EPI_QKV needs seq_len == qkv_dst_len > 0 and no fold consumer");
+    RC(op_seg_check("op_gemm_epi", a->seg_off, a->n_seq, M, a->qkv_dst_len));
+  }
   if (epi == EPI_QKV) {
     inner = a->heads * 64;
-    if (a->heads <= 0 || N != 3 * inner || a->seq_len <= 0 || M % a->seq_len || a->rope_heads < 0 ||
+    if (a->heads <= 0 || N != 3 * inner || a->seq_len <= 0 || (!rq && M % a->seq_len) || a->rope_heads < 0 ||
         a->rope_heads > a->heads || !a->q || !a->k || !a->v)
       return fail(F5H_EINVAL, "op_gemm_epi: EPI_QKV needs N == 3 * heads * 64, M % seq_len == 0 and q, k, v");
     if (a->qkv_dst_len != 0 && (a->qkv_dst_len < a->seq_len || a->ln_part_in))
@@ -2969,6 +3230,7 @@ int f5h_op_gemm_epi(void* stream, const f5h_op_gemm_args* a, void* workspace, si
     t.qkv_dst_len = a->qkv_dst_len;
     nqkv = (int64_t)qkv_dst_elems(t, M / a->seq_len);
   }
+  if (rq) nqkv = (int64_t)a->n_seq * a->heads * a->qkv_dst_len * 64;
   OpWs ws(workspace, workspace_bytes);
   void* wop = ws.take((size_t)Npad * K * es);
   void* aop = compute ? ws.take((size_t)nA * es) : nullptr;
@@ -2989,6 +3251,8 @@ int f5h_op_gemm_epi(void* stream, const f5h_op_gemm_args* a, void* workspace, si
       vop = ws.take((size_t)nqkv * es);
     }
   }
+  int32_t* rq_off = rq ? reinterpret_cast<int32_t*>(ws.take((size_t)(a->n_seq + 1) * 4)) : nullptr;
+  int2* rq_tab = rq ? reinterpret_cast<int2*>(ws.take((size_t)M * 8)) : nullptr;
   OPWS_CHECK(ws, "op_gemm_epi");
   HIPCK(hipMemsetAsync(wop, 0, (size_t)Npad * K * es, st));
   HIPCK(f32_to_op(compute, a->W, (int64_t)N * K, wop, st));
@@ -3021,6 +3285,11 @@ int f5h_op_gemm_epi(void* stream, const f5h_op_gemm_args* a, void* workspace, si
   g.add = a->add;
   g.ld_add = a->ld_add;
   g.dual_rows = dual;
+  if (rq) {
+    HIPCK(seg_upload(a->seg_off, a->n_seq + 1, rq_off, st));
+    HIPCK(build_rowtab(rq_off, a->n_seq, M, rq_tab, nullptr, st));
+    g.add = reinterpret_cast<const float*>(rq_tab);
+  }
   if (cop) {
     // in/out (EPI_RESID16): the rounded C goes in; write-only epilogues overwrite every element
     if (inout) HIPCK(f32_to_op(compute, a->C, nC, cop, st));

@@ -148,9 +148,12 @@ F5H_DEV V8 qk_norm8(V8 x, const V8& w, float eps, bool on);
 // Apply the epilogue to 8 consecutive columns [col, col+8) of output row `row`.
 // QKN (EPI_QKV, GemmArgs q_norm_w / k_norm_w): the head's RMSNorm on q and k, after the bias and before RoPE. The
 // callers' strips are 64 columns wide from a head start, so lanes 8i .. 8i + 7 hold one row's head (qk_norm8).
-template <typename TC, int EPI, bool QKN = false>
+// RQ (EPI_QKV over packed rows of unequal sequences, kernels.h qkv_rowtab): the row's (sequence, position) comes from
+// the per-row table instead of the division by seq_len; everything else is the same arithmetic.
+template <typename TC, int EPI, bool QKN = false, bool RQ = false>
 F5H_DEV void epi8(const GemmArgs& g, int row, int col, V8 x, const V8* pre = nullptr) {
   static_assert(!QKN || EPI == EPI_QKV, "qk_norm: the QKV epilogue");
+  static_assert(!RQ || EPI == EPI_QKV, "ragged rows: the QKV epilogue");
   const bool full = col + 8 <= g.N;
   if (g.bias) {
     if (full) {
@@ -168,7 +171,15 @@ F5H_DEV void epi8(const GemmArgs& g, int row, int col, V8 x, const V8* pre = nul
     const int inner = g.heads * 64;
     const int which = fdiv(col, inner), hc = col - which * inner;
     const int head = hc >> 6, dh = hc & 63;
-    const int s = fdiv(row, g.seq_len), pos = row - s * g.seq_len;
+    int s, pos;
+    if constexpr (RQ) {
+      const int2 sp = qkv_rowtab(g)[row];
+      s = sp.x;
+      pos = sp.y;
+    } else {
+      s = fdiv(row, g.seq_len);
+      pos = row - s * g.seq_len;
+    }
     if constexpr (QKN) x = qk_norm8(x, load8((which == 0 ? g.q_norm_w : g.k_norm_w) + dh), g.qk_norm_eps, which < 2);
     if (which < 2 && head < g.rope_heads) {
       const float4* cs = reinterpret_cast<const float4*>(g.rope + (int64_t)pos * 32 + (dh >> 1));
@@ -991,7 +1002,7 @@ F5H_DEV void epilogue_direct(const GemmArgs& g, const f32x4 (&acc)[MT][NT], int 
 // first operand load; blocks past the last tile (the chain pads each phase to whole XCD rounds) do nothing.
 // AUX: the cache policy of the strip epilogue's stores (kAuxWT: the write-through store policy, launch_cfg).
 template <typename TC, int EPI, int BM, int BN, int WGM, int WGN, int NS, bool FAST, int KB, bool PUB = false,
-          bool CHAIN = false, int AUX = 0, bool QKN = false>
+          bool CHAIN = false, int AUX = 0, bool QKN = false, bool RQ = false>
 F5H_DEV void gemm_body(const GemmArgs& g, const int b, const int nwg, uint4* lds, const ChainDep& dep) {
   const ProbeT probe_t = probe_enter(g.probe);
   typedef GemmCfg<BM, BN, WGM, WGN, NS, KB> C;
@@ -1243,6 +1254,7 @@ F5H_DEV void gemm_body(const GemmArgs& g, const int b, const int nwg, uint4* lds
   // chunk; measured 9.5 us of a 30.6 us QKV launch before).
   constexpr bool FAST_EPI = FAST && NT % 2 == 0;
   static_assert(FAST_EPI || !PUB, "the chain publishes after the fast (LDS-strip) epilogue");
+  static_assert(!RQ || !FAST_EPI, "ragged QKV rows: the general epilogue only");
   if constexpr (FAST_EPI) {
     static_assert(AUX == 0 || FAST_EPI, "the store policy exists for the strip epilogue only");
     epilogue_fast<TC, EPI, MT, NT, WN, C::EPAD, PREF, PUB ? kAuxWT : AUX, 1, !PUB, QKN>(
@@ -1266,7 +1278,7 @@ F5H_DEV void gemm_body(const GemmArgs& g, const int b, const int nwg, uint4* lds
         const float* src = Cs + rr * C::EPAD + cc * 8;
         float4 a = *reinterpret_cast<const float4*>(src), b = *reinterpret_cast<const float4*>(src + 4);
         if (row < g.M && col < g.N)
-          epi8<TC, EPI, QKN>(g, row, col, V8{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}}, PREF ? &pre[PREF ? i : 0][PREF ? t : 0] : nullptr);
+          epi8<TC, EPI, QKN, RQ>(g, row, col, V8{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}}, PREF ? &pre[PREF ? i : 0][PREF ? t : 0] : nullptr);
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -1277,10 +1289,10 @@ F5H_DEV void gemm_body(const GemmArgs& g, const int b, const int nwg, uint4* lds
 }
 
 template <typename TC, int EPI, int BM, int BN, int WGM, int WGN, int NS, bool FAST = false, int KB = 128, int AUX = 0,
-          bool QKN = false>
+          bool QKN = false, bool RQ = false>
 __global__ __launch_bounds__(64 * WGM * WGN, 2) void gemm_kernel(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) uint4 lds[GemmCfg<BM, BN, WGM, WGN, NS, KB>::bytes / 16];
-  gemm_body<TC, EPI, BM, BN, WGM, WGN, NS, FAST, KB, false, false, AUX, QKN>(g, blockIdx.x, gridDim.x, lds, ChainDep{});
+  gemm_body<TC, EPI, BM, BN, WGM, WGN, NS, FAST, KB, false, false, AUX, QKN, RQ>(g, blockIdx.x, gridDim.x, lds, ChainDep{});
 }
 
 // ======================================================================================
@@ -2093,9 +2105,40 @@ static hipError_t launch_qkn(const GemmArgs& a, int cfg, hipStream_t st) {
   return hipGetLastError();
 }
 
+// Ragged QKV launches (GemmArgs `add` = the per-row (sequence, position) table, kernels.h): the general epilogue of the
+// 64x128 tile (fp32) or the 128x128 tile (16-bit), with or without qk_norm, instantiated in gemm_rq.hip.
+hipError_t gemm_launch_rq_bf16(const GemmArgs& a, hipStream_t st);
+hipError_t gemm_launch_rq_f16(const GemmArgs& a, hipStream_t st);
+hipError_t gemm_launch_rq_f32(const GemmArgs& a, hipStream_t st);
+template <typename TC>
+static hipError_t launch_rq(const GemmArgs& a, hipStream_t st) {
+  constexpr int BM = is16<TC>() ? 128 : 64, NS = is16<TC>() ? 2 : 3;
+  const int tiles = ((a.M + BM - 1) / BM) * ((a.N + 127) / 128);
+  if (a.q_norm_w)
+    hipLaunchKernelGGL((gemm_kernel<TC, EPI_QKV, BM, 128, 2, 2, NS, false, 128, 0, true, true>), dim3(tiles), dim3(256), 0,
+                       st, a);
+  else
+    hipLaunchKernelGGL((gemm_kernel<TC, EPI_QKV, BM, 128, 2, 2, NS, false, 128, 0, false, true>), dim3(tiles), dim3(256),
+                       0, st, a);
+  return hipGetLastError();
+}
+
 template <typename TC, int EPI>
 static hipError_t launch_t(const GemmArgs& a, hipStream_t st) {
   if (a.M == 0) return hipSuccess;
+  if constexpr (EPI == EPI_QKV) {
+    if (a.add) {
+      // the panels must hold every position the table names (the caller built it from lengths <= qkv_dst_len); store
+      // addresses are 64-bit pointers here, no descriptor range to respect
+      const bool qkn = a.q_norm_w || a.k_norm_w;
+      if (a.ln_part_in || a.qkv_dst_len <= 0 || a.heads <= 0 || a.N != 3 * a.heads * 64 ||
+          (qkn && (!a.q_norm_w || !a.k_norm_w)))
+        return hipErrorInvalidValue;
+      if constexpr (std::is_same<TC, bf16>::value) return gemm_launch_rq_bf16(a, st);
+      else if constexpr (std::is_same<TC, float>::value) return gemm_launch_rq_f32(a, st);
+      else return gemm_launch_rq_f16(a, st);
+    }
+  }
   int cfg = 0;
   if constexpr (is16<TC>()) cfg = gemm_select_cfg(a);
   // the LayerNorm fold runs only in the strip epilogue of the 64-column-strip configurations (0, 1, 5, 11): a forced

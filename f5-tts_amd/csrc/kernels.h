@@ -108,7 +108,14 @@ struct GemmArgs {
   // as before. Tile configurations 12 and 13 have no such kernel and run as 11 (or 1), with the same bits.
   // (q_norm_w, qk_norm_eps: above)
   const float* k_norm_w;
+  // Ragged EPI_QKV (ragged sampling: packed rows of unequal sequences): `add` (EPI_INPROJ's field, unused by EPI_QKV)
+  // then points to a per-row table int2 (sequence, position) [M] (qkv_rowtab below): row m is rotated by rope[position]
+  // and stored at row `position` of the (sequence, head) panel, q / k / v [S, heads, qkv_dst_len, 64] (qkv_dst_len set:
+  // the longest sequence; seq_len unused). These launches run the general 8-column epilogue (epi8) of the 64x128 (fp32)
+  // or 128x128 (16-bit) tile, in instantiations of their own (gemm_impl.h RQ, gemm_rq.hip); every tile configuration
+  // gives the same bits, so each sequence has those of its own launch. Not with a fold consumer.
 };
+__host__ __device__ inline const int2* qkv_rowtab(const GemmArgs& g) { return reinterpret_cast<const int2*>(g.add); }
 static_assert(sizeof(GemmArgs) == 304, "GemmArgs: keep the kernel argument's size (see the layout note)");
 static_assert(offsetof(GemmArgs, qkv_dst_len) == offsetof(GemmArgs, ln_nparts) + 4 &&
                   offsetof(GemmArgs, ln_u) == offsetof(GemmArgs, ln_nparts) + 8,
@@ -190,7 +197,14 @@ struct AttnArgs {
   // Queries are unchanged (every row of [0, L), q_len, o_split). A separately compiled instantiation: launches
   // without kv_len2 run the kernels they always ran.
   const int32_t* kv_len2;
+  // Ragged output (o_split == kAttnRagged; ragged sampling): q / k / v stay padded panels [S, H, L, 64],
+  // but sequence s holds only kv_len[s] rows of its panels and its output row n goes to the packed row seg_off[s] + n of
+  // o [R, H*64], with seg_off = reinterpret_cast<const int32_t*>(o2) ([S], device). kv_len[s] is key length and live
+  // query length at once (q_len == kv_len, both set) and stands where L stands in the plain kernel, so panel rows past it
+  // are never read and each (sequence, head) has the bits of the plain kernel on that sequence alone at L = kv_len[s].
+  // Not with kv_len2. Separately compiled instantiations (attention.hip RO), as the two-range form's.
 };
+constexpr int kAttnRagged = -1;
 static_assert(sizeof(AttnArgs) == 120, "AttnArgs: keep the kernel argument's size (see the layout note)");
 hipError_t attention(int compute, const AttnArgs& a, hipStream_t st);
 int attention_store_wt(int compute, const AttnArgs& a, int want);  // as gemm_store_wt
@@ -200,6 +214,11 @@ void attention_force_safe(int on);
 // grouped conv1d k=31, 16 groups, pad 15 (ConvPositionEmbedding, modules.py:175-201)
 struct ConvArgs {
   const void* x; int x_f32;        // [S, L, d] input (fp32 or operand dtype)
+  // ragged (in the padding behind x_f32): x, resid and y are packed rows [R, d]; `rowkeep` is then the device segment
+  // table int32 off[S + 1] (reinterpreted), sequence s owns rows [off[s], off[s+1]) and taps outside them read zero;
+  // L = the longest sequence (the grid's extent), y_seq_stride / y_row_off are unused. Kernels of their own (conv.hip
+  // RAG): each sequence has the bits of the plain launch on that sequence alone
+  int ragged;
   const void* w;                   // packed [16][31][64 out][64 in] operand dtype
   const float* bias;               // [d]
   const uint8_t* rowkeep;          // [S*L] or null: input rows masked, output rows masked
@@ -228,7 +247,7 @@ hipError_t scale_cols(int compute, const void* W, int64_t rows, int K, const flo
 hipError_t rope_table(int L, float2* out, hipStream_t st);
 // text tokens -> embeddings (dit.py:86-120 / unett.py:53-64), both branches
 struct TextEmbArgs {
-  const int64_t* text; int B, nt, N, td;
+  const int64_t* text; int B, nt, N, td;  // (ragged: N = the packed rows R)
   const int32_t* seq_len;       // [B] per-sample valid length or null (= N for all)
   const float* table;           // [V, td]
   const float* freqs;           // [8192, td] or null (no sinus pos); [freq_rows, td] when freq_rows > 0
@@ -236,6 +255,9 @@ struct TextEmbArgs {
   int mask_padding;
   float* out_c; float* out_u;   // [B, N, td] each
   uint8_t* keep;                // [2B*N] !fill (for masked_fill after each block) or null
+  // ragged (or null): device segment table off[B + 1]; packed row off[b] + n is position n of utterance b, every row
+  // valid (seq_len unused); out_c / out_u are [R, td], keep [2R]
+  const int32_t* seg_off;
 };
 hipError_t text_embed(const TextEmbArgs& a, hipStream_t st);
 // text_embedding_average_upsampling (TextEmbedding.average_upsample_text_by_mask, dit.py:55-84): per sequence, the T
@@ -391,6 +413,13 @@ hipError_t mel_frames_ragged(const float* wav, int64_t wav_st, const int32_t* of
 // out[s][t][m] = log(max(mel[off[s] + t][m], 1e-5)) for t < T_s, exact 0 for T_s <= t < T_out ([B, T_out, n_mels])
 hipError_t mel_log_ragged(const float* mel, const int32_t* off, int B, int T_out, int n_mels, float* out,
                           hipStream_t st);
+// GRN over packed rows x [R, C] of S sequences (off[S + 1]): the norm of sequence s runs over its own rows, in 64-row
+// partial sums that start at the segment's first row and are added in the fixed order of `grn`, so each sequence has
+// grn's bits on that sequence alone. Lmax: the longest sequence. scratch: [(ceil(Lmax/64) + 1) * S * C] floats
+hipError_t grn_ragged(int compute, const float* x, const int32_t* off, int S, int R, int Lmax, int C,
+                      const float* gamma, const float* beta, float* scratch, void* out, hipStream_t st);
+// rowtab[m] = (sequence, position) of packed row m < R = off[S] (GemmArgs ragged EPI_QKV); len[s] = off[s+1] - off[s]
+hipError_t build_rowtab(const int32_t* off, int S, int R, int2* rowtab, int32_t* len, hipStream_t st);
 hipError_t f32_to_op(int compute, const float* x, int64_t n, void* out, hipStream_t st);
 hipError_t op_to_f32(int compute, const void* x, int64_t n, float* out, hipStream_t st);
 // Weight packing (engine creation): dst[i0*dst_st[0] + i1*dst_st[1] + i2*dst_st[2] + i3] =

@@ -36,6 +36,8 @@ EXPORTS = (
     "f5h_sample",
     "f5h_workspace_size_ode",
     "f5h_sample_ode",
+    "f5h_workspace_size_ragged",
+    "f5h_sample_ragged",
     "f5h_debug_ode_tableau",
     "f5h_debug_ode_eval_times",
     "f5h_forward",
@@ -66,6 +68,9 @@ EXPORTS = (
     "f5h_op_dwconv_ln_len",
     "f5h_op_grn",
     "f5h_op_grn_len",
+    "f5h_op_attention_ragged",
+    "f5h_op_conv_pos_ragged",
+    "f5h_op_grn_ragged",
     "f5h_op_gemm_epi",
     "f5h_op_text_upsample",
     "f5h_op_lnfold_uv",
@@ -159,6 +164,20 @@ class OpGemmArgs(ctypes.Structure):
         ("q_norm_w", ctypes.c_void_p), ("k_norm_w", ctypes.c_void_p), ("qk_norm_eps", ctypes.c_float),
         # rows of a destination (sequence, head) panel (0 = seq_len); read by a library with has_mmdit()
         ("qkv_dst_len", ctypes.c_int32),
+        # epi 7 over packed rows: HOST segment table [n_seq + 1] (null: none); read by a library with
+        # has_ragged_sampler()
+        ("seg_off", ctypes.c_void_p), ("n_seq", ctypes.c_int32),
+    ]
+
+
+class RaggedArgs(ctypes.Structure):
+    _fields_ = [
+        ("B", ctypes.c_int32), ("Lmax", ctypes.c_int32), ("nt", ctypes.c_int32), ("nfe", ctypes.c_int32),
+        ("R", ctypes.c_int64),
+        ("cond", ctypes.c_void_p), ("cond_mask", ctypes.c_void_p), ("text", ctypes.c_void_p),
+        ("duration", ctypes.c_void_p), ("y0", ctypes.c_void_p), ("t_grid", ctypes.c_void_p),
+        ("cfg_strength", ctypes.c_float),
+        ("out", ctypes.c_void_p), ("trajectory", ctypes.c_void_p),
     ]
 
 
@@ -315,6 +334,18 @@ def lib():
         L.f5h_mel_ragged_workspace_size.restype = sz
         L.f5h_mel_forward_ragged.argtypes = [vp, vp, i32, vp, i64, ctypes.POINTER(i32), i32, vp, vp, sz]
         L.f5h_mel_forward_ragged.restype = ctypes.c_int
+    if hasattr(L, "f5h_sample_ragged"):  # absent from an older build (has_ragged_sampler)
+        L.f5h_workspace_size_ragged.argtypes = [vp, i32, i64, i32, i32, i32, i32, i32]
+        L.f5h_workspace_size_ragged.restype = sz
+        L.f5h_sample_ragged.argtypes = [vp, vp, ctypes.POINTER(RaggedArgs), i32, vp, sz]
+        L.f5h_sample_ragged.restype = ctypes.c_int
+        pi32 = ctypes.POINTER(i32)
+        L.f5h_op_attention_ragged.argtypes = [vp, i32, i32, i32, i32, i32, pi32, vp, vp, vp, i32, vp, vp, sz]
+        L.f5h_op_attention_ragged.restype = ctypes.c_int
+        L.f5h_op_conv_pos_ragged.argtypes = [vp, i32, i32, i32, i32, i32, pi32, vp, vp, vp, i32, vp, i32, vp, vp, sz]
+        L.f5h_op_conv_pos_ragged.restype = ctypes.c_int
+        L.f5h_op_grn_ragged.argtypes = [vp, i32, i32, i32, i32, i32, pi32, vp, vp, vp, vp, vp, sz]
+        L.f5h_op_grn_ragged.restype = ctypes.c_int
     L.f5h_last_error.argtypes = []
     L.f5h_last_error.restype = ctypes.c_char_p
     L.f5h_version.argtypes = []
@@ -350,6 +381,12 @@ def has_ragged() -> bool:
     """False for an older build (F5H_LIB) without f5h_vocos_decode_ragged: such a library has no ragged batch
     entry points (Vocos.decode_ragged, MelSpec.forward_ragged)."""
     return hasattr(lib(), "f5h_vocos_decode_ragged")
+
+
+def has_ragged_sampler() -> bool:
+    """False for an older build (F5H_LIB) without f5h_sample_ragged: such a library has no ragged sampling path
+    (CFM.sample(ragged=True)), no ragged op hooks and ignores the seg_off field of the GEMM op hook."""
+    return hasattr(lib(), "f5h_sample_ragged")
 
 
 def check(rc: int, what: str = "f5h"):

@@ -105,6 +105,27 @@ def _mask_mode(arch: dict, use_batch_mask) -> int:
     return mode
 
 
+def _refuse_ragged(arch: dict) -> None:
+    """Ragged sampling (f5h_sample_ragged) serves the DiT backbone without text average upsampling. Everything else is
+    refused before any device work: NotImplementedError for a model the path does not serve, RuntimeError for an older
+    library (F5H_LIB) without the entry point."""
+    if arch["backbone"] != "DiT":
+        raise NotImplementedError(
+            f"ragged sampling serves the DiT backbone only, not {arch['backbone']}: UNetT carries a time-token row per "
+            "sequence and MMDiT a joint text-audio sequence, neither of which is packed (DESIGN.md §8); use "
+            "isolate=True")
+    if arch.get("text_embedding_average_upsampling"):
+        raise NotImplementedError("ragged sampling does not serve text_embedding_average_upsampling; use isolate=True")
+    if not _lib.has_ragged_sampler():
+        raise RuntimeError("the loaded libf5h.so has no f5h_sample_ragged (an older build): it cannot sample ragged "
+                           "batches (ragged=True)")
+
+
+def _seg_array(seg_off):
+    vals = [int(v) for v in seg_off]
+    return (ctypes.c_int32 * len(vals))(*vals), vals
+
+
 def _ode_method(method: str) -> int:
     if method not in _lib.ODE_METHOD:
         raise NotImplementedError(f"ode method {method!r}: the engine has 'euler', 'midpoint' and 'rk4'")
@@ -311,6 +332,60 @@ class Engine:
                            "f5h_sample")
         return out, traj
 
+    def workspace_bytes_ragged(self, durations, nt, nfe, use_cfg=True, method="euler", lmax=None) -> int:
+        """Bytes for a ragged call over utterances of `durations` frames (f5h_workspace_size_ragged)."""
+        _refuse_ragged(self.arch)
+        dur = [int(d) for d in durations]
+        return int(_lib.lib().f5h_workspace_size_ragged(self._h, len(dur), sum(dur), int(lmax or max(dur)), nt, nfe,
+                                                        int(use_cfg), _ode_method(method)))
+
+    def sample_ragged(self, cond, cond_mask, text, durations, y0, t_grid, cfg_strength, keep_trajectory=True,
+                      workspace=None, method="euler", lmax=None):
+        """The CFM ODE loop over B utterances as packed rows, no pad frames (f5h_sample_ragged; DiT). durations: HOST
+        ints [B], R = their sum; cond f32 [R,mel], cond_mask bool/u8 [R], y0 f32 [R,mel]: utterance b owns the rows
+        from sum(durations[:b]); text int64 [B,nt]. Returns (out [R,mel], trajectory [nfe+1,R,mel] or None). Every
+        utterance's rows equal its own B = 1 call bit for bit. lmax (default max(durations)): the geometry of the
+        per-utterance launches; calls with equal (B, R, lmax) replay one step graph whatever the lengths."""
+        _refuse_ragged(self.arch)
+        dur = _lib.host_ints(durations, len(durations), "durations")
+        B, R = len(dur), sum(dur)
+        lmax = int(lmax or max(dur))
+        mel = cond.shape[-1]
+        if tuple(cond.shape) != (R, mel) or tuple(y0.shape) != (R, mel) or cond_mask.numel() != R or text.shape[0] != B:
+            raise ValueError(f"ragged sample: packed tensors must hold R = {R} rows and text {B} rows")
+        nt = text.shape[1]
+        tg = np.ascontiguousarray(np.asarray(t_grid, dtype=np.float32))
+        nfe = tg.shape[0] - 1
+        cond = cond.to(self.device, torch.float32).contiguous()
+        cmask = cond_mask.to(self.device, torch.uint8).contiguous()
+        text = text.to(self.device, torch.int64).contiguous()
+        y0 = y0.to(self.device, torch.float32).contiguous()
+        out = torch.empty(R, mel, dtype=torch.float32, device=self.device)
+        traj = torch.empty(nfe + 1, R, mel, dtype=torch.float32, device=self.device) if keep_trajectory else None
+        use_cfg = cfg_strength >= 1e-5
+        m = _ode_method(method)
+        need = self.workspace_bytes_ragged(dur, nt, nfe, use_cfg, method, lmax)
+        if need == 0:  # the shape is outside the path: the call below names the reason
+            need = 256
+        stream = _lib.stream_handle(self.device)
+        if workspace is not None and workspace.numel() >= need:
+            ws, wlock = workspace, threading.Lock()
+        else:
+            ws, wlock = self._cached_workspace(need, stream)
+        darr = (ctypes.c_int32 * B)(*dur)
+        a = _lib.RaggedArgs()
+        a.B, a.Lmax, a.nt, a.nfe, a.R = B, lmax, nt, nfe, R
+        a.cond, a.cond_mask, a.text, a.y0 = cond.data_ptr(), cmask.data_ptr(), text.data_ptr(), y0.data_ptr()
+        a.duration = ctypes.cast(darr, ctypes.c_void_p).value
+        a.t_grid = tg.ctypes.data
+        a.cfg_strength = float(cfg_strength)
+        a.out = out.data_ptr()
+        a.trajectory = traj.data_ptr() if traj is not None else None
+        with torch.cuda.device(self.device), wlock:
+            _lib.check(_lib.lib().f5h_sample_ragged(self._h, stream, ctypes.byref(a), m, ws.data_ptr(), ws.numel()),
+                       "f5h_sample_ragged")
+        return out, traj
+
     def forward_workspace(self, B, N, nt, cfg_infer=True):
         """A workspace for `forward`; one kept across calls carries the text cache (text_cache=1/2)."""
         return self._workspace(self.workspace_bytes(B, N, nt, 1, cfg_infer))
@@ -473,6 +548,62 @@ def op_attention_ranges(Q, K, V, kv_len=None, kv_start2=0, kv_len2=None, q_len=N
     return O
 
 
+def op_attention_ragged(Q, K, V, seg_off, compute="bf16", q_prescaled=False):
+    """Attention over S sequences of unequal length with packed output rows (f5h_op_attention_ragged): Q, K, V padded
+    panels [S,H,Lmax,64] (rows past a sequence's length are never read), seg_off [S+1] host ints from 0 to R. Returns
+    O [R, H*64] (NaN where the kernel wrote nothing)."""
+    if not _lib.has_ragged_sampler():
+        raise RuntimeError("the loaded libf5h.so has no f5h_op_attention_ragged (an older build)")
+    S, H, Lmax, D = Q.shape
+    assert D == 64
+    arr, off = _seg_array(seg_off)
+    R = off[-1]
+    O = torch.full((R, H * 64), float("nan"), dtype=torch.float32, device=Q.device)
+    ws = torch.empty(Q.numel() * 6 + O.numel() * 2 + R * 8 + S * 8 + 4096, dtype=torch.uint8, device=Q.device)
+    _lib.check(_lib.lib().f5h_op_attention_ragged(_lib.stream_handle(Q.device), _lib.COMPUTE[compute], S, H, Lmax, R,
+                                                  arr, Q.contiguous().data_ptr(), K.contiguous().data_ptr(),
+                                                  V.contiguous().data_ptr(), int(bool(q_prescaled)), O.data_ptr(),
+                                                  ws.data_ptr(), ws.numel()), "f5h_op_attention_ragged")
+    return O
+
+
+def op_conv_pos_ragged(x, w, bias, seg_off, mode=0, resid=None, x_as_f32=True, compute="bf16"):
+    """One ConvPositionEmbedding layer over packed rows (f5h_op_conv_pos_ragged): x, resid [R,d], seg_off [S+1] host
+    ints; taps outside a row's own segment read zero. Returns y [R,d] (NaN where the kernel wrote nothing)."""
+    if not _lib.has_ragged_sampler():
+        raise RuntimeError("the loaded libf5h.so has no f5h_op_conv_pos_ragged (an older build)")
+    R, d = x.shape
+    dev = x.device
+    x, w, bias, resid = _f32(x), _f32(w, dev), _f32(bias, dev), _f32(resid, dev)
+    arr, off = _seg_array(seg_off)
+    S, lmax = len(off) - 1, max(b - a for a, b in zip(off, off[1:]))
+    y = torch.full((R, d), float("nan"), dtype=torch.float32, device=dev)
+    ws = torch.empty(16 * 31 * 64 * 64 * 4 + x.numel() * 4 + S * 4 + 4096, dtype=torch.uint8, device=dev)
+    _lib.check(_lib.lib().f5h_op_conv_pos_ragged(_lib.stream_handle(dev), _lib.COMPUTE[compute], S, lmax, R, d, arr,
+                                                 x.data_ptr(), w.data_ptr(), bias.data_ptr(), int(mode),
+                                                 _lib.ptr(resid), int(bool(x_as_f32)), y.data_ptr(), ws.data_ptr(),
+                                                 ws.numel()), "f5h_op_conv_pos_ragged")
+    return y
+
+
+def op_grn_ragged(x, gamma, beta, seg_off, compute="bf16"):
+    """GRN over packed rows (f5h_op_grn_ragged): x [R,C], seg_off [S+1] host ints; every sequence is normed over its
+    own rows. Returns out [R,C]."""
+    if not _lib.has_ragged_sampler():
+        raise RuntimeError("the loaded libf5h.so has no f5h_op_grn_ragged (an older build)")
+    R, C = x.shape
+    dev = x.device
+    x, gamma, beta = (_f32(t, dev) for t in (x, gamma, beta))
+    arr, off = _seg_array(seg_off)
+    S, lmax = len(off) - 1, max(b - a for a, b in zip(off, off[1:]))
+    out = torch.full((R, C), float("nan"), dtype=torch.float32, device=dev)
+    ws = torch.empty(((lmax + 63) // 64 + 1) * S * C * 4 + x.numel() * 2 + S * 4 + 4096, dtype=torch.uint8, device=dev)
+    _lib.check(_lib.lib().f5h_op_grn_ragged(_lib.stream_handle(dev), _lib.COMPUTE[compute], S, lmax, R, C, arr,
+                                            x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(),
+                                            ws.data_ptr(), ws.numel()), "f5h_op_grn_ragged")
+    return out
+
+
 def _f32(t, dev=None):
     return None if t is None else t.to(device=dev or t.device, dtype=torch.float32).contiguous()
 
@@ -568,7 +699,7 @@ def op_gemm_epi(epi, A, W, bias=None, C=None, compute="bf16", A2=None, k_split=0
                 live_len=None, live_seq=0, add=None, dual_rows=0, seq_len=0, heads=0, rope_heads=0, q_scale=0.0,
                 hs_scale=None, ln_producer=False, ln_part_in=None, ln_u=None, ln_v=None, ln_rms=False, ln_eps=0.0,
                 ln_nparts=None, poison=False, ws_fill=None, return_ws=False, q_norm_w=None, k_norm_w=None,
-                qk_norm_eps=1e-6, qkv_dst_len=0, qkv_bufs=None, qkv_row0=0):
+                qk_norm_eps=1e-6, qkv_dst_len=0, qkv_bufs=None, qkv_row0=0, seg_off=None):
     """A GEMM with epilogue `epi` (a key of EPI; f5h_op_gemm_epi). The in/out epilogues update a copy of C and
     return it; "inproj" returns C [M + dual_rows, N]; "qkv" returns (q, k, v [S,H,L,64], rope [L,32,2]).
 
@@ -583,7 +714,9 @@ def op_gemm_epi(epi, A, W, bias=None, C=None, compute="bf16", A2=None, k_split=0
     of every q / k head after the bias and ahead of RoPE; both None: no norm. qkv_dst_len ("qkv"; 0: none): the
     destination panels hold qkv_dst_len rows, q / k / v are [S,H,qkv_dst_len,64] — qkv_bufs (q, k, v), updated in place,
     or fresh NaN buffers — and the launch writes rows [qkv_row0, qkv_row0 + seq_len) of every panel (the pointers it
-    gets are advanced by qkv_row0 * 64 elements) and leaves the other rows alone."""
+    gets are advanced by qkv_row0 * 64 elements) and leaves the other rows alone. seg_off ("qkv"; host ints [S+1] from
+    0 to M): the rows are S packed sequences of unequal length; row seg_off[s] + n is rotated by rope[n] and stored at
+    row n of panel (s, head) of q / k / v [S,H,qkv_dst_len,64] (seq_len is then the rope table's rows, qkv_dst_len)."""
     M, K = A.shape
     N = W.shape[0]
     dev = A.device
@@ -614,10 +747,25 @@ def op_gemm_epi(epi, A, W, bias=None, C=None, compute="bf16", A2=None, k_split=0
     a.ln_rms, a.ln_eps, a.poison = int(bool(ln_rms)), float(ln_eps), int(bool(poison))
     out = None
     if epi == "qkv":
+        seg_arr = None
+        if seg_off is not None:
+            if not _lib.has_ragged_sampler():
+                raise RuntimeError("the loaded libf5h.so has no ragged QKV rows (an older build)")
+            seg_arr, segs = _seg_array(seg_off)
+            seq_len = int(qkv_dst_len)
         S = M // seq_len if seq_len > 0 else 0
         rope = torch.empty(max(seq_len, 0), 32, 2, dtype=torch.float32, device=dev)
         a.seq_len, a.heads, a.rope_heads, a.q_scale = int(seq_len), int(heads), int(rope_heads), float(q_scale)
-        if qkv_dst_len:
+        if seg_arr is not None:
+            S = len(segs) - 1
+            q, k, v = qkv_bufs if qkv_bufs is not None else (
+                torch.full((S, heads, qkv_dst_len, 64), float("nan"), dtype=torch.float32, device=dev)
+                for _ in range(3))
+            a.qkv_dst_len = int(qkv_dst_len)
+            a.seg_off, a.n_seq = ctypes.cast(seg_arr, ctypes.c_void_p).value, S
+            a.q, a.k, a.v, a.rope_out = q.data_ptr(), k.data_ptr(), v.data_ptr(), rope.data_ptr()
+            ws_bytes += 3 * S * heads * qkv_dst_len * 64 * 4 + M * 8 + S * 4 + 2048
+        elif qkv_dst_len:
             if not _lib.has_mmdit():
                 raise RuntimeError("the loaded libf5h.so has no qkv_dst_len (an older build)")
             assert 0 <= qkv_row0 and qkv_row0 + seq_len <= qkv_dst_len, "the launch's rows lie inside the panels"

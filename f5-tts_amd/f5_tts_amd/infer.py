@@ -275,7 +275,7 @@ def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_ty
 def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocoder, mel_spec_type="vocos",
                         progress=None, target_rms=0.1, cross_fade_duration=0.15, nfe_step=32, cfg_strength=2.0,
                         sway_sampling_coef=-1, speed=1, fix_duration=None, device=None, streaming=False,
-                        chunk_size=2048, batch_chunks=False):
+                        chunk_size=2048, batch_chunks=False, ragged=False):
     """utils_infer.py:440-596. Generator: yields `(wave, sr, spectrogram)` once (or, with
     `streaming`, `(wave_chunk, sr)` pieces of each batch in order). Per batch: duration
     = ref frames + ref frames / ref bytes * gen bytes / speed (speed 0.3 for < 10-byte text),
@@ -286,7 +286,8 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
     single calls -- the prompt's log-mel once (`model_obj.mel_spec`), one `model_obj.sample(..., isolate=True)` with
     host durations / lens, one `vocoder.decode_ragged`; no thread pool. An isolated batch computes every chunk as
     if it were sampled alone, so the wave, the spectrogram and the streaming pieces equal the thread-pool path's
-    (given the same noise per chunk)."""
+    (given the same noise per chunk). `ragged=True` (with `batch_chunks`): that batch goes as
+    `model_obj.sample(..., ragged=True)`, the same bits computed on the live frames only (DiT models)."""
     if mel_spec_type != "vocos":
         raise NotImplementedError("only the vocos mel/vocoder pair is on the HIP path")
     audio, sr = ref_audio
@@ -342,7 +343,7 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
                                             duration=torch.tensor(total, dtype=torch.long),
                                             lens=torch.tensor([frames] * n, dtype=torch.long), steps=nfe_step,
                                             cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef,
-                                            isolate=True)
+                                            **({"ragged": True} if ragged else {"isolate": True}))
             del _
             generated = generated.to(torch.float32)
             wavs = vocoder.decode_ragged(generated, [ref_audio_len] * n, [t - ref_audio_len for t in total])
@@ -392,7 +393,7 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
 
 def infer_batch(items, model_obj, vocoder, *, nfe_step=nfe_step, cfg_strength=cfg_strength,
                 sway_sampling_coef=sway_sampling_coef, speed=1.0, seed=None, target_rms=target_rms, max_batch=32,
-                isolate=False):
+                isolate=False, ragged=False):
     """Batch synthesis to waveforms, the reference's eval recipe (eval/utils_eval.py:109-148 and
     eval/eval_infer_batch.py:188-212) on ragged batches. `items`: `(ref_audio, ref_text, gen_text)` per utterance,
     `ref_audio` a WAV path or an `(audio [C, n] tensor, sr)` tuple as in `infer_process`. Per item: mono, RMS boost
@@ -403,6 +404,9 @@ def infer_batch(items, model_obj, vocoder, *, nfe_step=nfe_step, cfg_strength=cf
     one `vocoder.decode_ragged(out, ref, total - ref)`; the RMS boost is undone only where it was applied.
     `isolate=True`: `sample(..., isolate=True)`, every utterance computed as if it were sampled alone, so the result
     no longer depends on the bucketing (which utterances share a batch, and `max_batch`).
+    `ragged=True` (DiT models): `sample(..., ragged=True)`, the isolated batch computed on packed rows without pad
+    frames. Padding then costs nothing, so the items go in input order into batches of `max_batch`, no length buckets;
+    the waveforms are those of `isolate=True`, bit for bit.
     Returns `[(wave, 24000)]` in input order, `wave` a 1-D float32 numpy array of (total - ref - 1) * 256 samples."""
     from . import parallel
 
@@ -429,7 +433,11 @@ def infer_batch(items, model_obj, vocoder, *, nfe_step=nfe_step, cfg_strength=cf
                          total=total))
     waves = [None] * len(prep)
     with torch.inference_mode():
-        for b in parallel.bucket(range(len(prep)), [p["total"] for p in prep], max_batch):
+        if ragged:  # no pad frames to limit: batches of max_batch in input order
+            groups = [list(range(i, min(i + max_batch, len(prep)))) for i in range(0, len(prep), max_batch)]
+        else:
+            groups = parallel.bucket(range(len(prep)), [p["total"] for p in prep], max_batch)
+        for b in groups:
             cond, frames = model_obj.mel_spec.forward_ragged([prep[i]["audio"].to(device) for i in b])
             assert frames == [prep[i]["ref"] for i in b]
             ref = [prep[i]["ref"] for i in b]
@@ -439,7 +447,7 @@ def infer_batch(items, model_obj, vocoder, *, nfe_step=nfe_step, cfg_strength=cf
                                             duration=torch.tensor(total, dtype=torch.long),
                                             lens=torch.tensor(ref, dtype=torch.long), steps=nfe_step,
                                             cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed,
-                                            **({"isolate": True} if isolate else {}))
+                                            **({"ragged": True} if ragged else {"isolate": True} if isolate else {}))
             del _
             for i, wav in zip(b, vocoder.decode_ragged(generated, ref, [t - r for t, r in zip(total, ref)])):
                 if prep[i]["rms"] < target_rms:

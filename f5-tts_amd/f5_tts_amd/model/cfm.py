@@ -58,6 +58,21 @@ def _to_device(vals, device):
     return t.to(device)
 
 
+def _unpack_ragged(out_p, traj_p, dur_host, max_duration):
+    """Packed rows [R, mel] (and [T, R, mel]) of a ragged call -> the padded [B, Nmax, mel] (and [T, B, Nmax, mel]) of
+    the batched call, rows past each utterance's duration exactly zero."""
+    B, mel = len(dur_host), out_p.shape[-1]
+    out = out_p.new_zeros(B, max_duration, mel)
+    traj = None if traj_p is None else traj_p.new_zeros(traj_p.shape[0], B, max_duration, mel)
+    r = 0
+    for b, d in enumerate(dur_host):
+        out[b, :d] = out_p[r:r + d]
+        if traj is not None:
+            traj[:, b, :d] = traj_p[:, r:r + d]
+        r += d
+    return out, traj
+
+
 class CFM(nn.Module):
     def __init__(self, transformer: nn.Module, sigma=0.0, odeint_kwargs: dict = dict(method="euler"),
                  audio_drop_prob=0.3, cond_drop_prob=0.2, num_channels=None, mel_spec_module: nn.Module | None = None,
@@ -107,19 +122,27 @@ class CFM(nn.Module):
     def sample(self, cond, text, duration, *, lens=None, steps=32, cfg_strength=1.0, sway_sampling_coef=None,
                seed: int | None = None, max_duration=65536, vocoder: Callable | None = None, use_epss=True,
                no_ref_audio=False, duplicate_test=False, t_inter=0.1, edit_mask=None, y0=None,
-               keep_trajectory: bool = True, isolate: bool = False):
+               keep_trajectory: bool = True, isolate: bool = False, ragged: bool = False):
         """Same arguments/returns as the reference `CFM.sample`; extra keyword `y0` supplies the
         initial noise explicitly (parity tests), `keep_trajectory=False` skips the [steps+1,...] copy.
         `isolate=True`: every utterance of a batch is sampled as if it were alone (f5h.h use_batch_mask == 2), so its
         frames below its duration do not depend on what else is in the batch (the reference's padded batch leaks: pad
-        keys, GRN over the padded axis, unmasked conv position embeddings); with one utterance it is the plain call."""
+        keys, GRN over the padded axis, unmasked conv position embeddings); with one utterance it is the plain call.
+        `ragged=True` (DiT): the isolated batch computed on packed rows, without the pad frames (f5h_sample_ragged):
+        the same bits as `isolate=True` below every utterance's duration and exact zeros past it, in the same shapes;
+        with one utterance it is the plain call. UNetT, MMDiT and text average upsampling raise NotImplementedError."""
         if self.training:
             self.eval()
         arch = getattr(self.transformer, "arch", None)
+        if ragged:  # refused before any device work (an older library: RuntimeError)
+            from ..engine import _refuse_ragged
+
+            _refuse_ragged(arch if arch is not None else {"backbone": type(self.transformer).__name__})
+            ragged = cond.shape[0] > 1  # one utterance: the plain call, the same launches
         if arch is not None:  # MMDiT with attn_mask_enabled and a plain batch mask, or isolation on an older library:
             from ..engine import _mask_mode, _refuse_mmdit_masked  # refused before any device work
 
-            mode = (2 if isolate else 1) if cond.shape[0] > 1 else 0
+            mode = 0 if ragged else (2 if isolate else 1) if cond.shape[0] > 1 else 0
             _refuse_mmdit_masked(arch, mode)
             _mask_mode(arch, mode)
         pdtype = next(self.parameters()).dtype
@@ -196,8 +219,17 @@ class CFM(nn.Module):
         t_host = t.float().numpy()
 
         eng = self.transformer.get_engine(self.engine_compute(), self.device)
-        out, traj = eng.sample(cond.float(), cond_mask, text, duration, y0.float(), t_host, float(cfg_strength),
-                               use_batch_mask, keep_trajectory=keep_trajectory, method=self.ode_method)
+        if ragged:
+            # the valid rows of the padded batch, concatenated: cond, cond_mask and the noise of utterance b are its
+            # rows below dur_host[b] (edit_mask, no_ref_audio and the duplicate_test mix are already in them)
+            pack = lambda x: torch.cat([x[b, :d] for b, d in enumerate(dur_host)], dim=0)  # noqa: E731
+            out_p, traj_p = eng.sample_ragged(pack(cond.float()), pack(cond_mask), text, dur_host, pack(y0.float()),
+                                              t_host, float(cfg_strength), keep_trajectory=keep_trajectory,
+                                              method=self.ode_method)
+            out, traj = _unpack_ragged(out_p, traj_p, dur_host, max_duration)
+        else:
+            out, traj = eng.sample(cond.float(), cond_mask, text, duration, y0.float(), t_host, float(cfg_strength),
+                                   use_batch_mask, keep_trajectory=keep_trajectory, method=self.ode_method)
         out = out.to(pdtype)
         if traj is not None:
             traj = traj.to(pdtype)

@@ -117,7 +117,7 @@ def plan(totals, world: int, max_batch: int):
 
 
 def run_sharded(utts, sample_fn, *, rank: int, world: int, max_batch: int = 32, device=None, group=None,
-                plan_all=None, vocoder=None):
+                plan_all=None, vocoder=None, ragged=False):
     """Run a whole utterance job data-parallel and return {index: generated mel [total-ref, C]} on
     every rank; with a `vocoder` (the HIP `Vocos`, or any object with `decode_ragged` and `hop_length`), each
     batch is decoded ragged straight from the sampler's output and the dict holds the waves instead,
@@ -127,7 +127,8 @@ def run_sharded(utts, sample_fn, *, rank: int, world: int, max_batch: int = 32, 
     frames) and `total` (total frames), the fields of one prompt in eval_infer_batch.py:182-185.
     sample_fn(cond [B,Nc,C], text list, duration LongTensor[B], lens LongTensor[B]) -> out [B,N,C]: the
     engine's `CFM.sample` (or a stand-in in tests). `plan_all` (from `plan`, every rank's batches) may be
-    passed to reuse a plan across calls. World 1 runs without any collective."""
+    passed to reuse a plan across calls. World 1 runs without any collective. `ragged=True`: every batch is sampled
+    as `sample_fn(cond, text, duration, lens, ragged=True)` (`CFM.sample`'s keyword: packed rows, no pad frames)."""
     if plan_all is None:
         plan_all = plan([u["total"] for u in utts], world, max_batch)
     batches = plan_all[rank]
@@ -142,7 +143,7 @@ def run_sharded(utts, sample_fn, *, rank: int, world: int, max_batch: int = 32, 
         # lengths stay host tensors: CFM.sample evaluates its duration rule on the host without a sync
         dur = torch.tensor([utts[i]["total"] for i in b], dtype=torch.long)
         lens = torch.tensor([utts[i]["ref"] for i in b], dtype=torch.long)
-        out = sample_fn(cond, text, dur, lens)
+        out = sample_fn(cond, text, dur, lens, ragged=True) if ragged else sample_fn(cond, text, dur, lens)
         if vocoder is not None:
             waves = vocoder.decode_ragged(out, lens, dur - lens)
             local.update(zip(b, waves))

@@ -197,6 +197,36 @@ size_t f5h_workspace_size_ode(const f5h_engine* eng, int32_t B, int32_t N, int32
                               int32_t use_cfg, int32_t method);
 int f5h_sample_ode(f5h_engine* eng, void* stream, const f5h_sample_args* args, int32_t method, void* workspace,
                    size_t workspace_bytes);
+/* Ragged sampling (DiT; DESIGN.md §3 'Ragged sampling'): the B utterances of a call as packed rows, no pad frames.
+ * R = sum of duration[b]; utterance b owns rows [off[b], off[b] + duration[b]) of every packed tensor, off the running
+ * sum. The engine runs the 2R rows of both CFG branches (the conditional half first); the kernels that reach across
+ * rows (QKV epilogue, attention, conv position embedding, the text embedding's ConvNeXt blocks) work per segment, so
+ * every utterance's rows equal its own B = 1 call bit for bit (with the LayerNorm fold off there; ragged calls never
+ * fold or chain), hence also the use_batch_mask == 2 batch over the rows below duration[b].
+ * duration is a HOST array, consumed before the call returns (the segment tables are uploaded by kernel argument); every
+ * other pointer is a device pointer except t_grid. Lmax >= every duration (the geometry of the per-segment launches
+ * and the q / k / v panels): the step graph is keyed by (B, R, Lmax), not by the lengths, so calls with the same three
+ * numbers replay one graph. F5H_EINVAL: a backbone other than DiT, text_average_upsampling, a duration below 1 or above
+ * Lmax, durations that do not add up to R, Lmax above 8192, 2 R at or above 2^24. The solver argument is
+ * f5h_sample_ode's. Their presence tells a caller that the library samples ragged batches. */
+typedef struct f5h_ragged_args {
+  int32_t B, Lmax, nt, nfe;
+  int64_t R;
+  const float* cond;         /* [R,mel] packed cond mel */
+  const uint8_t* cond_mask;  /* [R] */
+  const int64_t* text;       /* [B,nt] token ids, -1 = pad */
+  const int32_t* duration;   /* HOST [B] frames per utterance, each in [1, Lmax] */
+  const float* y0;           /* [R,mel] initial noise */
+  const float* t_grid;       /* HOST [nfe+1] */
+  float cfg_strength;
+  float* out;                /* [R,mel] */
+  float* trajectory;         /* [nfe+1,R,mel] or NULL */
+} f5h_ragged_args;
+size_t f5h_workspace_size_ragged(const f5h_engine* eng, int32_t B, int64_t R, int32_t Lmax, int32_t nt, int32_t steps,
+                                 int32_t use_cfg, int32_t method);
+int f5h_sample_ragged(f5h_engine* eng, void* stream, const f5h_ragged_args* args, int32_t method, void* workspace,
+                      size_t workspace_bytes);
+
 /* Test hooks (host only, no device needed). f5h_debug_ode_tableau: the Butcher tableau the solver kernel is
  * instantiated with: *stages, stage times c[4], stage matrix a[16] (row-major 4x4, strictly lower), weights b[4];
  * entries past the method's stages are 0. f5h_debug_ode_eval_times: the steps x stages evaluation times the engine
@@ -477,6 +507,13 @@ typedef struct f5h_op_gemm_args {
    * and leaves the others as the caller's buffers hold them (the hook pre-fills its 16-bit staging from them). Refused
    * below seq_len and with a fold consumer. */
   int32_t qkv_dst_len;
+  /* epi 7 over packed rows of unequal sequences (read by a library that exports f5h_sample_ragged; NULL: none): seg_off
+   * is a HOST table [n_seq + 1], 0 = seg_off[0] < ... < seg_off[n_seq] = M, every length <= qkv_dst_len; row m of
+   * sequence s at position n = m - seg_off[s] is rotated by rope[n] and stored at row n of panel (s, head) of q, k, v
+   * [n_seq, heads, qkv_dst_len, 64]; seq_len must equal qkv_dst_len (the rope table's rows). Panel rows past a
+   * sequence's length come back as the caller's buffers hold them. No fold consumer. */
+  const int32_t* seg_off;
+  int32_t n_seq;
 } f5h_op_gemm_args;
 #define F5H_OP_GUARD_ROWS 4
 int f5h_op_gemm_epi(void* stream, const f5h_op_gemm_args* args, void* workspace, size_t workspace_bytes);
@@ -501,6 +538,22 @@ int f5h_op_lnfold_uv(void* stream, int32_t compute, int32_t nfe, int32_t depth, 
  * buffers, g [K]. K % 8 == 0. */
 int f5h_op_scale_cols(void* stream, int32_t compute, int64_t rows, int32_t K, const float* W, const float* g,
                       float* out, void* workspace, size_t workspace_bytes);
+
+/* The ragged forms of the three ops that reach across rows, over S sequences as packed rows: seg_off is a HOST table
+ * [S + 1] from 0 to R with every length in [1, Lmax]. Each sequence's rows equal, bit for bit, the plain op on that
+ * sequence alone (f5h_op_attention at N = its length, f5h_op_conv_pos at S = 1, L = its length, f5h_op_grn likewise).
+ * Attention: Q, K, V are padded panels [S, H, Lmax, 64] of which sequence s holds seg_len[s] rows (the rest is never
+ * read and may hold NaN); O [R, H*64] packed. Conv: x, resid, y [R, d] packed, taps outside a row's own segment read
+ * zero; mode and x_as_f32 as f5h_op_conv_pos. GRN: x, out [R, C] packed. */
+int f5h_op_attention_ragged(void* stream, int32_t compute, int32_t S, int32_t H, int32_t Lmax, int32_t R,
+                            const int32_t* seg_off, const float* Q, const float* K, const float* V,
+                            int32_t q_prescaled, float* O, void* workspace, size_t workspace_bytes);
+int f5h_op_conv_pos_ragged(void* stream, int32_t compute, int32_t S, int32_t Lmax, int32_t R, int32_t d,
+                           const int32_t* seg_off, const float* x, const float* w, const float* bias, int32_t mode,
+                           const float* resid, int32_t x_as_f32, float* y, void* workspace, size_t workspace_bytes);
+int f5h_op_grn_ragged(void* stream, int32_t compute, int32_t S, int32_t Lmax, int32_t R, int32_t C,
+                      const int32_t* seg_off, const float* x, const float* gamma, const float* beta, float* out,
+                      void* workspace, size_t workspace_bytes);
 
 /* Tuning/test hook: pin the 16-bit GEMM tile configuration for all later launches in this
  * process (0, 1, 5, 11, 12, 13), or -1 to restore the automatic per-shape choice. */
