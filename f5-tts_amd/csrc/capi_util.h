@@ -1,4 +1,4 @@
-// Shared host-side helpers of the C ABI translation units (engine.cpp, vocos.cpp).
+// Shared host-side helpers of the C ABI translation units (engine_ctl.cpp defines them; vocos.cpp, melspec.cpp).
 #pragma once
 #include <string>
 

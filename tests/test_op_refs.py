@@ -4,7 +4,7 @@ deliberately wrong float64 variant (op_reference.WRONG_*) misses it on at least 
 set. A variant that slipped through would mean the inputs are too tame to expose that mistake in a kernel.
 
 Also here: the new op entry points refuse shapes outside their launchers' contracts with F5H_EINVAL before any
-device work. The conv weight packing (pack_conv_weight, engine.cpp) runs as a device kernel and cannot be called
+device work. The conv weight packing (pack_conv_weight, engine_pack.cpp) runs as a device kernel and cannot be called
 on the host; it is covered by the GPU conv tests, which pass the torch-layout weight through it.
 """
 
