@@ -407,12 +407,26 @@ def infer_batch(items, model_obj, vocoder, *, nfe_step=nfe_step, cfg_strength=cf
     `ragged=True` (DiT models): `sample(..., ragged=True)`, the isolated batch computed on packed rows without pad
     frames. Padding then costs nothing, so the items go in input order into batches of `max_batch`, no length buckets;
     the waveforms are those of `isolate=True`, bit for bit.
+    An item may carry a fourth element, a dict with `speed` and / or `seed`, which override the call's values for that
+    item, in every mode: `speed` enters the item's own duration, and a batch with a `seed` override draws every
+    utterance's noise from its own seed (`sample(..., seed=[...])`). With `isolate=True` or `ragged=True` the item's
+    waveform is then that of its own single run with those settings. Any other key raises ValueError before any work.
     Returns `[(wave, 24000)]` in input order, `wave` a 1-D float32 numpy array of (total - ref - 1) * 256 samples."""
     from . import parallel
 
     device = getattr(model_obj, "device", None) or _default_device()
+    overs = []
+    for k, item in enumerate(items):  # the per-item settings, checked before any work
+        over = dict(item[3]) if len(item) > 3 and item[3] else {}
+        bad = sorted(set(over) - {"speed", "seed"})
+        if bad:
+            raise ValueError(f"item {k}: per-item setting(s) {bad} are not served (an item may override speed and "
+                             "seed; the sampler settings are shared by a batch)")
+        overs.append(over)
     prep = []
-    for k, (ref_audio, ref_text, gen_text) in enumerate(items):
+    for k, item in enumerate(items):
+        ref_audio, ref_text, gen_text = item[:3]
+        speed_k = overs[k].get("speed", speed)
         audio, sr = load_audio(ref_audio) if isinstance(ref_audio, str) else ref_audio
         if audio.ndim == 1:
             audio = audio[None]
@@ -426,7 +440,7 @@ def infer_batch(items, model_obj, vocoder, *, nfe_step=nfe_step, cfg_strength=cf
         if len(ref_text[-1].encode("utf-8")) == 1:
             ref_text = ref_text + " "
         ref = 1 + audio.shape[-1] // hop_length  # the prompt's mel frames (torch.stft center=True)
-        total = ref + int(ref / len(ref_text.encode("utf-8")) * len(gen_text.encode("utf-8")) / speed)
+        total = ref + int(ref / len(ref_text.encode("utf-8")) * len(gen_text.encode("utf-8")) / speed_k)
         if total <= ref:
             raise ValueError(f"item {k}: nothing to generate ({len(gen_text.encode('utf-8'))} bytes of gen_text)")
         prep.append(dict(audio=audio[0], rms=rms, text=convert_char_to_pinyin([ref_text + gen_text])[0], ref=ref,
@@ -442,11 +456,13 @@ def infer_batch(items, model_obj, vocoder, *, nfe_step=nfe_step, cfg_strength=cf
             assert frames == [prep[i]["ref"] for i in b]
             ref = [prep[i]["ref"] for i in b]
             total = [prep[i]["total"] for i in b]
+            # a batch with a per-item seed draws every utterance's noise from its own seed
+            seed_b = [overs[i].get("seed", seed) for i in b] if any("seed" in overs[i] for i in b) else seed
             # lengths stay host tensors: CFM.sample evaluates its duration rule on the host without a sync
             generated, _ = model_obj.sample(cond=cond, text=[prep[i]["text"] for i in b],
                                             duration=torch.tensor(total, dtype=torch.long),
                                             lens=torch.tensor(ref, dtype=torch.long), steps=nfe_step,
-                                            cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed,
+                                            cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed_b,
                                             **({"ragged": True} if ragged else {"isolate": True} if isolate else {}))
             del _
             for i, wav in zip(b, vocoder.decode_ragged(generated, ref, [t - r for t, r in zip(total, ref)])):

@@ -73,6 +73,23 @@ def _unpack_ragged(out_p, traj_p, dur_host, max_duration):
     return out, traj
 
 
+def _seed_list(seed, batch):
+    """The entries of a per-utterance `seed` (a list, a tuple or a CPU tensor with one entry per utterance; an entry
+    may be None), or None when `seed` is one value for the whole call (an int, None, a 0-dim tensor)."""
+    if torch.is_tensor(seed):
+        if seed.ndim == 0:
+            return None
+        if seed.device.type != "cpu":
+            raise ValueError(f"per-utterance seeds must be host values (a list, a tuple or a CPU tensor), not a tensor "
+                             f"on {seed.device}")
+        seed = seed.reshape(-1).tolist()
+    elif not isinstance(seed, (list, tuple)):
+        return None
+    if len(seed) != batch:
+        raise ValueError(f"per-utterance seed has {len(seed)} entries for {batch} utterances")
+    return [None if v is None else int(v) for v in seed]
+
+
 class CFM(nn.Module):
     def __init__(self, transformer: nn.Module, sigma=0.0, odeint_kwargs: dict = dict(method="euler"),
                  audio_drop_prob=0.3, cond_drop_prob=0.2, num_channels=None, mel_spec_module: nn.Module | None = None,
@@ -130,9 +147,14 @@ class CFM(nn.Module):
         keys, GRN over the padded axis, unmasked conv position embeddings); with one utterance it is the plain call.
         `ragged=True` (DiT): the isolated batch computed on packed rows, without the pad frames (f5h_sample_ragged):
         the same bits as `isolate=True` below every utterance's duration and exact zeros past it, in the same shapes;
-        with one utterance it is the plain call. UNetT, MMDiT and text average upsampling raise NotImplementedError."""
+        with one utterance it is the plain call. UNetT, MMDiT and text average upsampling raise NotImplementedError.
+        `seed` also takes one entry per utterance (a list, a tuple or a CPU tensor, in every mode): utterance b's
+        noise is drawn after `torch.manual_seed(seed[b])`, as its own call with that seed would draw it (a None entry
+        draws without reseeding); a list of the wrong length raises ValueError before any device work. An int seeds
+        every utterance alike, as before."""
         if self.training:
             self.eval()
+        seeds = _seed_list(seed, cond.shape[0])
         arch = getattr(self.transformer, "arch", None)
         if ragged:  # refused before any device work (an older library: RuntimeError)
             from ..engine import _refuse_ragged
@@ -202,9 +224,10 @@ class CFM(nn.Module):
 
         if y0 is None:  # noise recipe of cfm.py:196-201 (per utterance, same seed each)
             ys = []
-            for dur in dur_host:
-                if exists(seed):
-                    torch.manual_seed(seed)
+            for b, dur in enumerate(dur_host):
+                sd = seed if seeds is None else seeds[b]
+                if exists(sd):
+                    torch.manual_seed(sd)
                 ys.append(torch.randn(dur, self.num_channels, device=self.device, dtype=pdtype))
             y0 = pad_sequence(ys, padding_value=0, batch_first=True)
 
