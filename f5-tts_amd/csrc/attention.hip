@@ -65,15 +65,8 @@ F5H_DEV float xor32(float x) {
 // round-robin over the 8 XCDs (MI355X_MICROARCH.md, dispatch); giving each XCD a contiguous run
 // of logical ids keeps all query blocks of one (sequence, head) on one L2, so its K/V leave
 // MALL/HBM once instead of once per XCD (bijective form, cdna_hip_programming.md T1).
-F5H_DEV void attn_block(int& qb, int& bh) {
-  const int nqb = gridDim.x, nwg = gridDim.x * gridDim.y;
-  const int w = blockIdx.x + nqb * blockIdx.y;
-  const int xq = nwg >> 3, xr = nwg & 7, xcd = w & 7;
-  const int id = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (w >> 3);
-  qb = id % nqb;
-  bh = id / nqb;
-}
-
+// (the map itself is in attn16_kernel's launch head: logical id = the XCD's run start + w / 8, then
+// (qb, bh) = (id % nqb, id / nqb) by the launcher's multiply-shift constants)
 // RSM: row sums on the matrix pipe (l^T += ones . P^T, one 32x32x16 MFMA per 16-key chunk) instead of 16 packed
 // VALU adds per tile (F5H_ATTN_ROWSUM=mfma; an A/B switch, results agree to rounding)
 // WT: the store policy's write-through form of the O store (AttnArgs::store_wt; a separately compiled kernel, so
@@ -88,49 +81,72 @@ F5H_DEV void attn_block(int& qb, int& bh) {
 // so a (sequence, head) runs the instructions of the plain kernel on that sequence alone and rows of the panel past
 // its length are never read; O row n of sequence s is packed row seg_off[s] + n.
 template <typename T, bool PRESCALED, int NW, bool RSM, bool WT = false, bool RG = false, bool RO = false>
-__global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
+__global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs) {  // (read through kernarg_at below)
   typedef Op16<T> OP;
   typedef typename OP::v8 v8;
   typedef typename OP::v4 v4;
-  const ProbeT probe_t = probe_enter(a.probe);
   constexpr int TILE_B = 2 * 64 * 128;  // K + V tile bytes (64 keys x 64 dh x 2 B each)
   constexpr int NS = 4;                 // LDS ring: one tile read while three are in flight
   constexpr int CPW = 512 / (64 * NW);  // 16-B chunks of one K (or V) tile per lane
   constexpr float THR = 8.f;
   static_assert(CPW * 64 * NW == 512, "whole DMA rounds");
   __shared__ __attribute__((aligned(16))) uint4 lds[NS * TILE_B / 16];
+  // ---- Launch head (DESIGN.md §3 'Launch head'): the hot line of the arguments (kernels.h) as ONE batch of scalar
+  // loads, pinned here by the empty asm (hipcc otherwise sinks every argument load to its first use, one memory round
+  // trip each); then the workgroup's (query block, sequence, head), the liveness tests, and tile 0's DMA. Every other
+  // argument is read through a copy of the argument pointer made opaque behind the batch (a1) and again behind the
+  // prologue's loads (a, below), so that none of those loads can be hoisted in front of either.
+  const KArgP<AttnArgs> ka = kernarg_at<AttnArgs>(0);
+  const T* const Qp = reinterpret_cast<const T*>(ka->q);
+  const T* const Kp = reinterpret_cast<const T*>(ka->k);
+  const T* const Vp = reinterpret_cast<const T*>(ka->v);
+  const int S = ka->S, H = ka->H, aL = ka->L, kv_start2 = ka->kv_start2;
+  const unsigned flags = ka->head_flags, nqb_mul = ka->head_nqb_mul, h_mul = ka->head_h_mul;
+  asm volatile("" ::"s"(Qp), "s"(Kp), "s"(Vp), "s"(S), "s"(H), "s"(aL), "s"(kv_start2), "s"(flags), "s"(nqb_mul),
+               "s"(h_mul));
+  const AttnArgs& a1 = karg_after(ka);
+  __builtin_amdgcn_sched_barrier(0);
+  const ProbeT probe_t = probe_enter(a1.probe, __builtin_expect((flags & kAttnHeadProbe) != 0, 0));
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int h = lane >> 5;
-  int qb, bh;
-  attn_block(qb, bh);
+  // XCD-aware map (above): the grid is nqb query blocks x S * H (sequence, head) pairs
+  const int nqb = (aL + 32 * NW - 1) / (32 * NW), nbh = S * H, nwg = nqb * nbh;
+  const int w = blockIdx.x + nqb * blockIdx.y;
+  const int xq = nwg >> 3, xr = nwg & 7, xcd = w & 7;
+  const int id = xcd * xq + min(xcd, xr) + (w >> 3);
+  int bh = (int)magic_div((unsigned)id, nqb_mul, (flags >> kAttnHeadShiftQb) & 31u);
+  const int qb = id - bh * nqb;
+  const bool has_qlen = (flags & kAttnHeadQ) != 0;
   // with the pad skip, dead query blocks cluster by sequence length: deal the (sequence, head) pairs over
   // the XCDs round-robin so every XCD holds a share of every length (all blocks of a pair stay on one XCD)
-  if (a.q_len) bh = spread8(bh, gridDim.y);
-  const int s_idx = bh / a.H, head = bh - s_idx * a.H;
-  int Lseq = a.L;
-  if constexpr (RO) Lseq = __builtin_amdgcn_readfirstlane(max(0, min(a.L, a.kv_len[s_idx])));
+  if (__builtin_expect(has_qlen, 0)) bh = spread8(bh, nbh);
+  const int s_idx = (int)magic_div((unsigned)bh, h_mul, (flags >> kAttnHeadShiftH) & 31u), head = bh - s_idx * H;
+  int Lseq = aL;
+  if constexpr (RO) Lseq = __builtin_amdgcn_readfirstlane(max(0, min(aL, a1.kv_len[s_idx])));
   const int L = Lseq;
-  if (a.q_len && qb * (32 * NW) >= a.q_len[s_idx]) {  // dead query block (pad rows only): nothing to write
-    probe_exit(a.probe, probe_t);
+  // Dead query blocks leave before any DMA is issued: a wave that ended with LDS-DMA in flight would write into LDS
+  // the next workgroup owns.
+  if (__builtin_expect(has_qlen, 0) && qb * (32 * NW) >= a1.q_len[s_idx]) {  // dead query block (pad rows only): nothing to write
+    probe_exit(a1.probe, probe_t, w);
     return;
   }
   if constexpr (RO) {
     if (qb * (32 * NW) >= L) {  // (q_len is the same length on the ragged path; an empty sequence writes nothing)
-      probe_exit(a.probe, probe_t);
+      probe_exit(a1.probe, probe_t, w);
       return;
     }
   }
-  const int64_t base = (int64_t)bh * (RO ? a.L : L) * 64;
-  const T* Q = reinterpret_cast<const T*>(a.q) + base;
-  const T* K = reinterpret_cast<const T*>(a.k) + base;
-  const T* V = reinterpret_cast<const T*>(a.v) + base;
+  const int64_t base = (int64_t)bh * (RO ? aL : L) * 64;
+  const T* Q = Qp + base;
+  const T* K = Kp + base;
+  const T* V = Vp + base;
   int klen = L;
-  if (a.kv_len) klen = min(klen, a.kv_len[s_idx]);
+  if (__builtin_expect((flags & kAttnHeadKv) != 0, 0)) klen = min(klen, a1.kv_len[s_idx]);
   int nt1 = 0, start2 = 0, end2 = 0;  // RG only
   if constexpr (RG) {
-    start2 = __builtin_amdgcn_readfirstlane(max(0, min(a.kv_start2, L)));
+    start2 = __builtin_amdgcn_readfirstlane(max(0, min(kv_start2, L)));
     klen = __builtin_amdgcn_readfirstlane(max(0, min(klen, start2)));
-    end2 = __builtin_amdgcn_readfirstlane(start2 + max(0, min(a.kv_len2[s_idx], L - start2)));
+    end2 = __builtin_amdgcn_readfirstlane(start2 + max(0, min(a1.kv_len2[s_idx], L - start2)));
     nt1 = (klen + 63) / 64;
   }
   const int ntile = RG ? nt1 + (end2 - start2 + 63) / 64 : (klen + 63) / 64;
@@ -184,6 +200,27 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
     }
   };
 
+  // Tile 0's K/V, then Q, then tiles 1 and 2: one counted wait covers tile 0 and Q together (in
+  // order), so Q's latency overlaps tile 0's instead of preceding it. Q is loaded by inline asm (hipcc
+  // would wait vmcnt(0), draining tiles 1 and 2, before its first use) and released by the wait below.
+  // Tiles 1 and 2 are issued even past the end of short rows (clamped rows into unused ring slots; the
+  // last tile's vmcnt(0) drains them) so that the count of loads behind Q is fixed.
+  dma(0, 0);
+  u32x4 q0, q1, q2, q3;
+  {
+    // rows past L are clamped (their outputs are never stored)
+    const T* qp = Q + (int64_t)min(qrow, L - 1) * 64 + h * 8;
+    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(q0) : "v"(qp) : "memory");
+    asm volatile("global_load_dwordx4 %0, %1, off offset:32" : "=v"(q1) : "v"(qp) : "memory");
+    asm volatile("global_load_dwordx4 %0, %1, off offset:64" : "=v"(q2) : "v"(qp) : "memory");
+    asm volatile("global_load_dwordx4 %0, %1, off offset:96" : "=v"(q3) : "v"(qp) : "memory");
+  }
+  dma(1, 1);
+  dma(2, 2);
+  // the prologue's loads are issued: the rest of the setup (LDS read addresses, accumulators) runs under their
+  // latency, ahead of the counted wait (no vector memory access in it, so hipcc puts no vmcnt wait of its own here)
+  const AttnArgs& a = karg_after(ka);
+  __builtin_amdgcn_sched_barrier(0);
   const uint32_t lds0 = (uint32_t)(uintptr_t)(LDS_PTR(void))lds;
   uint32_t kaddr[4];
 #pragma unroll
@@ -219,23 +256,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
     minit[r] = 0.f;
   }
 
-  // Tile 0's K/V, then Q, then tiles 1 and 2: one counted wait covers tile 0 and Q together (in
-  // order), so Q's latency overlaps tile 0's instead of preceding it. Q is loaded by inline asm (hipcc
-  // would wait vmcnt(0), draining tiles 1 and 2, before its first use) and released by the wait below.
-  // Tiles 1 and 2 are issued even past the end of short rows (clamped rows into unused ring slots; the
-  // last tile's vmcnt(0) drains them) so that the count of loads behind Q is fixed.
-  dma(0, 0);
-  u32x4 q0, q1, q2, q3;
-  {
-    // rows past L are clamped (their outputs are never stored)
-    const T* qp = Q + (int64_t)min(qrow, L - 1) * 64 + h * 8;
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(q0) : "v"(qp) : "memory");
-    asm volatile("global_load_dwordx4 %0, %1, off offset:32" : "=v"(q1) : "v"(qp) : "memory");
-    asm volatile("global_load_dwordx4 %0, %1, off offset:64" : "=v"(q2) : "v"(qp) : "memory");
-    asm volatile("global_load_dwordx4 %0, %1, off offset:96" : "=v"(q3) : "v"(qp) : "memory");
-  }
-  dma(1, 1);
-  dma(2, 2);
+  __builtin_amdgcn_sched_barrier(0);
   asm volatile("s_waitcnt vmcnt(%4)" : "+v"(q0), "+v"(q1), "+v"(q2), "+v"(q3) : "i"(4 * CPW) : "memory");
   const u32x4 qv[4] = {q0, q1, q2, q3};
   v8 qf[4];
@@ -251,7 +272,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
   // per-wave dead rows (batch path pad skip, q_len): a wave whose 32 query rows all lie past q_len keeps its
   // share of the K/V DMA and the barriers (the ring is shared by the workgroup) but computes and stores
   // nothing, so its SIMD partner issues alone (waves w and w + 4 share a SIMD; the dead rows are the last ones)
-  const bool wave_dead = a.q_len && (qb * (32 * NW) + wid_s * 32) >= a.q_len[s_idx];
+  const bool wave_dead = has_qlen && (qb * (32 * NW) + wid_s * 32) >= a.q_len[s_idx];
   constexpr float LMAX = std::is_same<T, f16>::value ? 32768.f : 0x1p64f;  // fp16 P must stay below 65504
 
   // One K/V tile. FIRST (tile 0): the running max m_run starts at the tile's row max. Later tiles are
@@ -277,7 +298,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
   // first half: K fragments, the DMA of tile kt+3, S^T = K.Q^T - m_run, ragged-tile mask, FIRST / SAFE max
   auto tile_qk = [&](auto SLOT, auto FIRST_, auto SAFE_, const int kt) __attribute__((always_inline)) {
     constexpr bool FIRST = decltype(FIRST_)::value, SAFE = decltype(SAFE_)::value;
-    if (FIRST && !SAFE) probe_mark(a.probe, probe_t, 1);
+    if (FIRST && !SAFE) probe_mark(a.probe, probe_t, 1, w);
     constexpr int slot = decltype(SLOT)::value;
     constexpr uint32_t so = (uint32_t)(slot * TILE_B);  // ring slot offset: an immediate of every LDS read
 
@@ -499,7 +520,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
       if constexpr (WT) __syncthreads();
     }
   }
-  probe_mark(a.probe, probe_t, 2);
+  probe_mark(a.probe, probe_t, 2, w);
   const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
   // Epilogue (T21): lane l < 32 holds columns 8k..8k+3 of its row, lane l + 32 columns 8k+4..8k+7; one
   // permlane32 swap per dword pairs groups k and k+1, so every lane stores 16 contiguous bytes
@@ -571,7 +592,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn16_kernel(AttnArgs a) {
       }
     }
   }
-  probe_exit(a.probe, probe_t);
+  probe_exit(a.probe, probe_t, w);
 }
 
 // ---------------------------------------------------------------- fp32 parity kernel
@@ -721,6 +742,7 @@ hipError_t attention(int compute, const AttnArgs& a0, hipStream_t st) {
   }
   AttnArgs a = a0;
   a.force_safe = g_force_safe;
+  if (compute != F5H_C_FP32 && !attn_head_fill(a, 256)) return hipErrorInvalidValue;  // (launch16's query blocks)
   if (store_policy_forced() >= 0) a.store_wt = attention_store_wt(compute, a0, store_policy_forced());
   switch (compute) {
     case F5H_C_BF16: launch16<bf16>(a, st); break;

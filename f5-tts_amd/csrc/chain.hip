@@ -96,20 +96,20 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(Launch L) {
   d.tl = (L.a.probe.tl && pt.k == 0 && b < kTimelineWG) ? L.a.probe.tl + (size_t)b * 4 : nullptr;
   if (d.tl && threadIdx.x == 0) d.tl[1] = d.tl[2] = 0ull;
   if (p == 0) {
-    gemm_body<TC, EPI_RESID16, kOutBM, kBN, 2, 2, 3, true, 128, true, true>(L.a.out, b, L.start[1], lds, d);
+    gemm_body<TC, EPI_RESID16, kOutBM, kBN, 2, 2, 3, true, 128, true, true>(kernarg_at<GemmArgs>(offsetof(Launch, a) + offsetof(ChainArgs, out)), b, lds, d);
   } else if (p == 1) {
     ln_phase<TC>(L.a.ln1, M, b - L.start[1], d);
   } else if (p == 2) {
-    gemm_body<TC, EPI_GELU_TANH, kFf1BM, kBN, 2, 2, 2, true, 128, true, true>(L.a.ff1, b - L.start[2],
-                                                                               L.start[3] - L.start[2], lds, d);
+    gemm_body<TC, EPI_GELU_TANH, kFf1BM, kBN, 2, 2, 2, true, 128, true, true>(
+        kernarg_at<GemmArgs>(offsetof(Launch, a) + offsetof(ChainArgs, ff1)), b - L.start[2], lds, d);
   } else if (p == 3) {
-    gemm_body<TC, EPI_RESID16, kFf2BM, kBN, 2, 2, 3, true, 128, true, true>(L.a.ff2, b - L.start[3],
-                                                                             L.start[4] - L.start[3], lds, d);
+    gemm_body<TC, EPI_RESID16, kFf2BM, kBN, 2, 2, 3, true, 128, true, true>(
+        kernarg_at<GemmArgs>(offsetof(Launch, a) + offsetof(ChainArgs, ff2)), b - L.start[3], lds, d);
   } else if (p == 4) {
     ln_phase<TC>(L.a.ln2, M, b - L.start[4], d);
   } else {
-    gemm_body<TC, EPI_QKV, kQkvBM, kBN, 2, 2, 2, true, 128, false, true>(L.a.qkv, b - L.start[5],
-                                                                          L.start[6] - L.start[5], lds, d);
+    gemm_body<TC, EPI_QKV, kQkvBM, kBN, 2, 2, 2, true, 128, false, true>(
+        kernarg_at<GemmArgs>(offsetof(Launch, a) + offsetof(ChainArgs, qkv)), b - L.start[5], lds, d);
   }
   probe_exit(L.a.probe, pt);
 }
@@ -144,6 +144,11 @@ hipError_t chain_launch(int compute, const ChainArgs& a, hipStream_t st) {
   L.start[0] = 0;
   for (int p = 0; p < 6; ++p) L.start[p + 1] = L.start[p] + round8(cnt[p]);
   if (!a.fault) return hipErrorInvalidValue;
+  // the GEMM phases' launch heads (kernels.h): a phase's workgroups are its padded share of the grid
+  if (!gemm_head_fill(L.a.out, L.start[1] - L.start[0], kBN) || !gemm_head_fill(L.a.ff1, L.start[3] - L.start[2], kBN) ||
+      !gemm_head_fill(L.a.ff2, L.start[4] - L.start[3], kBN) ||
+      (qkv && !gemm_head_fill(L.a.qkv, L.start[6] - L.start[5], kBN)))
+    return hipErrorInvalidValue;
   const unsigned spin_limit = (unsigned)g_spin_limit.load(std::memory_order_relaxed);
   // producers' arrivals per complete row group: a GEMM tile adds 1 to each group it covers (its row block
   // spans whole groups), so a group is complete at (column tiles) arrivals; a LayerNorm unit covers half a group

@@ -127,30 +127,35 @@ struct ProbeT {
   unsigned long long t0;
   int k;
 };
-F5H_DEV ProbeT probe_enter(const f5h::DevProbe& p) {
+// on: p.slots != null, where the caller already holds that (the launch heads' flag word: no load of p.slots on the
+// way to the first operand DMA)
+F5H_DEV ProbeT probe_enter(const f5h::DevProbe& p, bool on) {
   ProbeT r{0ull, -1};
-  if (p.slots) {
+  if (on) {
     r.k = *p.tick;
     r.t0 = wall_clock64();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   }
   return r;
 }
+F5H_DEV ProbeT probe_enter(const f5h::DevProbe& p) { return probe_enter(p, p.slots != nullptr); }
 // timeline stamp `idx` of this workgroup (wave 0's view; only in the timeline launch)
-F5H_DEV void probe_mark(const f5h::DevProbe& p, const ProbeT& r, int idx) {
+// wg: the workgroup's linear index in the grid where the caller holds it (the kernels with a launch head: no load of
+// the hidden grid size); -1: from the grid
+F5H_DEV void probe_mark(const f5h::DevProbe& p, const ProbeT& r, int idx, int wg = -1) {
   if (p.tl && r.k == 0 && threadIdx.x == 0) {
-    const int wg = blockIdx.x + gridDim.x * blockIdx.y;
+    if (wg < 0) wg = blockIdx.x + gridDim.x * blockIdx.y;
     if (wg < f5h::kTimelineWG) p.tl[wg * 4 + idx] = idx == 0 ? r.t0 : (unsigned long long)wall_clock64();
   }
 }
-F5H_DEV void probe_exit(const f5h::DevProbe& p, const ProbeT& r) {
+F5H_DEV void probe_exit(const f5h::DevProbe& p, const ProbeT& r, int wg = -1) {
   if (p.slots && (threadIdx.x & 63) == 0 && r.k >= 0 && r.k < f5h::kProbeTicks && r.k % f5h::kProbeEvery == 0) {
     const int64_t i = probe_slot(r.k);
     atomicMax(p.slots + f5h::kProbeEnd + i, (unsigned long long)wall_clock64());
     if (threadIdx.x == 0) atomicMin(p.slots + i, r.t0);
   }
-  probe_mark(p, r, 0);
-  probe_mark(p, r, 3);
+  probe_mark(p, r, 0, wg);
+  probe_mark(p, r, 3, wg);
 }
 
 F5H_DEV float gelu_erf(float x) {  // nn.GELU(), modules.py:266 (explicit rounding, see gelu_tanh_fast)
@@ -312,6 +317,25 @@ F5H_DEV void buffer_store16(__amdgpu_buffer_rsrc_t r, uint32_t off, u32x4 v) {
 // host pass from emitting the kernel's launch stub.
 F5H_DEV void dma16(__amdgpu_buffer_rsrc_t r, LDS_PTR(void) dst, uint32_t voff, uint32_t soff) {
   __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, voff, soff, 0, 0);
+}
+
+// A kernel's by-value argument struct T at byte `off` of its kernel-argument segment, as a pointer into the
+// constant address space (scalar loads). Device-only wrappers, as dma16: the builtin in a kernel body would keep
+// hipcc's host pass from emitting the kernel's launch stub.
+template <typename T>
+using KArgP = const __attribute__((address_space(4))) T*;
+template <typename T>
+F5H_DEV KArgP<T> kernarg_at(size_t off) {
+  return (KArgP<T>)((const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + off);
+}
+// The same arguments through a pointer the compiler cannot see through: loads through the result stay behind this
+// point in program order (and behind every side effect before it), where hipcc would otherwise hoist argument loads
+// to the kernel's entry or sink them to their uses as it pleases. (No memory clobber: it would make every later load
+// from global memory through an argument pointer a vector load, where hipcc proves no store can precede it now.)
+template <typename T>
+F5H_DEV const T& karg_after(KArgP<T> p) {
+  asm volatile("" : "+s"(p));
+  return *(const T*)p;
 }
 
 template <int B, int E, typename F>

@@ -166,7 +166,7 @@ struct ProbeScope {
 static GemmArgs gargs(const void* A, int64_t lda, const Lin& W, int M, void* C, int64_t ldc) {
   GemmArgs g{};
   g.A = A;
-  g.lda = lda;
+  g.lda = (int)lda;
   g.W = W.w;
   g.ldw = W.K;
   g.M = M;

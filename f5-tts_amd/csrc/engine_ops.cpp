@@ -85,6 +85,23 @@ int f5h_debug_tile_live(const int32_t* live_len, int32_t live_seq, int32_t M, in
   return tile_live_rows(live_len, live_seq, M, m0, BM) ? 1 : 0;
 }
 
+int64_t f5h_debug_magic_div_sweep(uint32_t n_end, uint32_t d_lo, uint32_t d_hi, uint32_t* limits) {
+  if (limits) {
+    limits[0] = kMagicMaxN;
+    limits[1] = kMagicMaxD;
+  }
+  if (d_lo == 0 || d_hi < d_lo || n_end > 0x7fffffffu) return -1;
+  int64_t bad = 0;
+  for (uint32_t d = d_lo; d <= d_hi; ++d) {
+    const MagicDiv m = magic_div_make(d);
+    for (uint32_t n = 0; n < n_end; ++n) {
+      const uint32_t q = magic_div(n, m.mul, m.shift);
+      bad += (q != n / d) | (n - q * d != n % d);
+    }
+  }
+  return bad;
+}
+
 static int op_attention_impl(void* stream, int32_t compute, int32_t S, int32_t H, int32_t N, const float* Q,
                              const float* K, const float* V, const int32_t* kv_len, const int32_t* q_len,
                              int32_t q_prescaled, float* O, void* workspace, size_t workspace_bytes,
@@ -434,6 +451,8 @@ int f5h_op_gemm_epi(void* stream, const f5h_op_gemm_args* a, void* workspace, si
       return fail(F5H_EINVAL, "op_gemm_epi: EPI_INPROJ needs N % 8 == 0, an addend with ld_add % 8 == 0 and no bias");
     dual = a->dual_rows;
     if (dual != 0 && dual < M) return fail(F5H_EINVAL, "op_gemm_epi: dual_rows must be 0 or >= M");
+    if (a->ld_add > 0x7fffffff || dual > 0x7fffffff)
+      return fail(F5H_EINVAL, "op_gemm_epi: ld_add and dual_rows are 32-bit in the launch arguments");
   } else if (a->add || a->dual_rows) {
     return fail(F5H_EINVAL, "op_gemm_epi: add / dual_rows go with EPI_INPROJ");
   }
@@ -562,8 +581,8 @@ int f5h_op_gemm_epi(void* stream, const f5h_op_gemm_args* a, void* workspace, si
   g.live_len = a->live_len;
   g.live_seq = a->live_len ? a->live_seq : 0;
   g.add = a->add;
-  g.ld_add = a->ld_add;
-  g.dual_rows = dual;
+  g.ld_add = (int)a->ld_add;
+  g.dual_rows = (int)dual;
   if (rq) {
     HIPCK(seg_upload(a->seg_off, a->n_seq + 1, rq_off, st));
     HIPCK(build_rowtab(rq_off, a->n_seq, M, rq_tab, nullptr, st));

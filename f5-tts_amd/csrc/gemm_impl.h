@@ -273,10 +273,10 @@ F5H_DEV void epi8(const GemmArgs& g, int row, int col, V8 x, const V8* pre = nul
       for (int e = 0; e < 8; ++e) o0.v[e] = x.v[e] + a0.v[e];
       store8<float>(C + off, o0);
       if (g.dual_rows) {
-        V8 a1 = load8(g.add + ao + g.dual_rows * g.ld_add);
+        V8 a1 = load8(g.add + ao + (int64_t)g.dual_rows * g.ld_add);
 #pragma unroll
         for (int e = 0; e < 8; ++e) o1.v[e] = x.v[e] + a1.v[e];
-        store8<float>(C + off + g.dual_rows * g.ldc, o1);
+        store8<float>(C + off + (int64_t)g.dual_rows * g.ldc, o1);
       }
       return;
     }
@@ -996,15 +996,14 @@ F5H_DEV void epilogue_direct(const GemmArgs& g, const f32x4 (&acc)[MT][NT], int 
 // + 144 AGPR = 260: one block per CU, so the C2 QKV GEMM (480 tiles) ran as two rounds on 256 CUs
 // (tools/timeline_c2.py: second half of the grid entering 24 us after the first). Declaring 2 waves
 // per SIMD it fits in 212 VGPR, no spill.
-// The block body of gemm_kernel: block b of nwg (XCD-remapped below) computes one BM x BN tile in the LDS
-// image `lds`. PUB (the in-launch phase chain, chain.hip): stores are write-through and the tile's row groups are
+// The block body of gemm_kernel: block b of the arguments' head_nwg (XCD-remapped below) computes one BM x BN tile
+// in the LDS image `lds`; `ka`: the arguments where they lie in the kernel-argument segment. PUB (the in-launch phase chain, chain.hip): stores are write-through and the tile's row groups are
 // published to dep.pub; a non-null dep.wait makes the block wait for its row groups' producers before its
 // first operand load; blocks past the last tile (the chain pads each phase to whole XCD rounds) do nothing.
 // AUX: the cache policy of the strip epilogue's stores (kAuxWT: the write-through store policy, launch_cfg).
 template <typename TC, int EPI, int BM, int BN, int WGM, int WGN, int NS, bool FAST, int KB, bool PUB = false,
           bool CHAIN = false, int AUX = 0, bool QKN = false, bool RQ = false>
-F5H_DEV void gemm_body(const GemmArgs& g, const int b, const int nwg, uint4* lds, const ChainDep& dep) {
-  const ProbeT probe_t = probe_enter(g.probe);
+F5H_DEV void gemm_body(const KArgP<GemmArgs> ka, const int b, uint4* lds, const ChainDep& dep) {
   typedef GemmCfg<BM, BN, WGM, WGN, NS, KB> C;
   constexpr int E = elems16<TC>();
   constexpr int CPR = C::CPR, SLABS = KB / 64;
@@ -1016,28 +1015,51 @@ F5H_DEV void gemm_body(const GemmArgs& g, const int b, const int nwg, uint4* lds
   typedef typename Slab<TC>::frag frag;
   auto swz = [](int row, int chunk) { return KB == 128 ? swz128g(row, chunk) : swz64(row, chunk); };
 
+  // ---- Launch head (DESIGN.md §3 'Launch head'): the hot line of the arguments (kernels.h) as ONE batch of scalar
+  // loads, then only what the first operand stages need -- tile origin, the two extents, the lanes' offsets -- and
+  // the stages are issued; everything else of the setup runs while they are in flight. The empty asm pins the batch
+  // here (hipcc otherwise sinks every argument load to its first use, one memory round trip each, behind branches);
+  // every other argument is read through a copy of the argument pointer made opaque behind the batch (g1) and again
+  // behind the first stages (g, below), so that none of those loads can be hoisted in front of either.
+  const TC* const A = reinterpret_cast<const TC*>(ka->A);
+  const TC* const W = reinterpret_cast<const TC*>(ka->W);
+  const TC* const A2 = reinterpret_cast<const TC*>(ka->A2);
+  const int lda = ka->lda, ldw = ka->ldw, M = ka->M, N = ka->N, K = ka->K, k_split = ka->k_split;
+  const unsigned flags = ka->head_flags, ntn_mul = ka->head_ntn_mul;
+  const int nwg = ka->head_nwg, ntn = ka->head_ntn;
+  asm volatile("" ::"s"(A), "s"(W), "s"(A2), "s"(lda), "s"(ldw), "s"(M), "s"(N), "s"(K), "s"(k_split), "s"(flags),
+               "s"(ntn_mul), "s"(nwg), "s"(ntn));
+  const GemmArgs& g1 = karg_after(ka);
+  __builtin_amdgcn_sched_barrier(0);
+  const ProbeT probe_t = probe_enter(g1.probe, __builtin_expect((flags & kHeadProbe) != 0, 0));
+
+  const int wg_lin = CHAIN ? -1 : b;  // (gemm_kernel's grid is one-dimensional: b is the workgroup's linear index)
   constexpr int stage_u4 = C::stage_bytes / 16;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WGN, wn = wid % WGN;
-  const int ntn = (g.N + BN - 1) / BN;
   // XCD-aware remap (cdna_hip_programming.md T1, bijective form): blocks b and b+8 share an
   // XCD, so give each XCD a contiguous run of n-fastest tiles -> its L2 holds whole A panels
+  // (XCD x's run starts at x * xq + min(x, xr): the first xr runs are one longer)
   const int xq = nwg >> 3, xr = nwg & 7, xcd = b & 7;
-  const int bid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (b >> 3);
+  const int bid = xcd * xq + min(xcd, xr) + (b >> 3);
   if constexpr (CHAIN) {
-    if (bid >= ((g.M + BM - 1) / BM) * ntn) return;
+    if (bid >= ((M + BM - 1) / BM) * ntn) return;
   }
-  // with the pad skip, row tiles of padding cluster by sequence: spread the m-rows over the XCDs
-  const int mrow = g.live_len ? spread8(bid / ntn, (g.M + BM - 1) / BM) : bid / ntn;
-  const int m0 = mrow * BM, n0 = (bid % ntn) * BN;
-  if constexpr (EPI == EPI_RESID || EPI == EPI_RESID16) {
-    if (!tile_live(g, m0, BM)) {  // every row padding: nothing to add (C2's B = 1 never passes live_len)
-      probe_exit(g.probe, probe_t);
-      return;
+  int mrow = (int)magic_div((unsigned)bid, ntn_mul, flags >> kHeadShift);
+  const int n0 = (bid - mrow * ntn) * BN;
+  // Pad-row skip (live_len; C2's B = 1 never passes it): decided before any DMA is issued -- a wave that ended with
+  // LDS-DMA in flight would write into LDS the next workgroup owns.
+  if (__builtin_expect((flags & kHeadLive) != 0, 0)) {
+    // row tiles of padding cluster by sequence: spread the m-rows over the XCDs
+    mrow = spread8(mrow, (M + BM - 1) / BM);
+    if constexpr (EPI == EPI_RESID || EPI == EPI_RESID16) {
+      if (!tile_live(g1, mrow * BM, BM)) {  // every row padding: nothing to add
+        probe_exit(g1.probe, probe_t, wg_lin);
+        return;
+      }
     }
   }
-  const TC* A = reinterpret_cast<const TC*>(g.A);
-  const TC* W = reinterpret_cast<const TC*>(g.W);
+  const int m0 = mrow * BM;
 
   // LDS-DMA by buffer_load ... lds against per-block buffers (the block's A rows and W rows): a lane's byte
   // offset in its panel is fixed across K-steps (voffset; the swizzle goes on the SOURCE chunk so that the
@@ -1046,31 +1068,33 @@ F5H_DEV void gemm_body(const GemmArgs& g, const int b, const int nwg, uint4* lds
   // buffer and read as zero; they feed only unstored outputs.
   const int wid_s = __builtin_amdgcn_readfirstlane(wid);
   constexpr int ESZ = (int)sizeof(TC);
-  const uint32_t abytes = (uint32_t)(min(BM, g.M - m0) * g.lda * ESZ);
-  const uint32_t wbytes = (uint32_t)(min(BN, g.N - n0) * g.ldw * ESZ);
+  const uint32_t abytes = (uint32_t)(min(BM, M - m0) * lda * ESZ);
+  const uint32_t wbytes = (uint32_t)(min(BN, N - n0) * ldw * ESZ);
+  // DMA round i covers rows [i * RPR, (i + 1) * RPR) of the panel: the lane's row moves by RPR (a multiple of the
+  // swizzle's period), its chunk stays, so every round's offset is round 0's plus i * RPR rows
+  constexpr int RPR = C::THREADS / CPR;
+  static_assert(RPR % 16 == 0, "the swizzled chunk of a lane is the same in every DMA round");
+  const int row0 = tid / CPR, chunk0 = swz(row0, tid % CPR) * E;
   uint32_t aoff[AR], boff[BR];
   static_for<0, AR>([&](auto I) {
     constexpr int i = decltype(I)::value;
-    const int p = (i * NW + wid) * 64 + lane, row = p / CPR, slot = p % CPR;
-    aoff[i] = (uint32_t)((row * g.lda + swz(row, slot) * E) * ESZ);
+    aoff[i] = (uint32_t)(((row0 + i * RPR) * lda + chunk0) * ESZ);
   });
   static_for<0, BR>([&](auto I) {
     constexpr int i = decltype(I)::value;
-    const int p = (i * NW + wid) * 64 + lane, row = p / CPR, slot = p % CPR;
-    boff[i] = (uint32_t)((row * g.ldw + swz(row, slot) * E) * ESZ);
+    boff[i] = (uint32_t)(((row0 + i * RPR) * ldw + chunk0) * ESZ);
   });
   // A columns [k_split, K) come from the second panel A2 (cat(x, skip) of UNetT, unett.py:288-297):
   // a stage never straddles k_split (a multiple of the stage width)
-  const TC* A2 = reinterpret_cast<const TC*>(g.A2);
   const __amdgpu_buffer_rsrc_t wrs =
-      rsrc_of(W + (int64_t)n0 * g.ldw, wbytes);
+      rsrc_of(W + (int64_t)n0 * ldw, wbytes);
   auto stage_a = [&](int buf, int k0) {
     uint4* As = lds + buf * stage_u4;
-    const bool second = A2 && k0 >= g.k_split;
+    const bool second = A2 && k0 >= k_split;
     const TC* Ab = second ? A2 : A;
-    const int ka = second ? k0 - g.k_split : k0;
+    const int ka = second ? k0 - k_split : k0;
     const __amdgpu_buffer_rsrc_t ars =
-        rsrc_of(Ab + (int64_t)m0 * g.lda, abytes);
+        rsrc_of(Ab + (int64_t)m0 * lda, abytes);
     static_for<0, AR>([&](auto I) {
       constexpr int i = decltype(I)::value;
       dma16(ars, (LDS_PTR(void))(As + (i * NW + wid_s) * 64), aoff[i], ka * ESZ);
@@ -1087,6 +1111,22 @@ F5H_DEV void gemm_body(const GemmArgs& g, const int b, const int nwg, uint4* lds
     stage_a(buf, k0);
     stage_w(buf, k0);
   };
+
+  const int nk = K / BKE;
+  if constexpr (CHAIN) {
+    // phase chain: the weight panels of the first stages (no producer in the launch) are in flight while the
+    // block waits for its rows; the activation panels follow the acquire. Issue order W0 .. W(NS-2), A0 ..
+    // A(NS-2): the first wait below counts activation pieces only.
+    for (int p = 0; p < NS - 1 && p < nk; ++p) stage_w(p, p * BKE);
+    chain_wait(dep, M, m0, BM);
+    for (int p = 0; p < NS - 1 && p < nk; ++p) stage_a(p, p * BKE);
+  } else {
+    for (int p = 0; p < NS - 1 && p < nk; ++p) stage(p, p * BKE);
+  }
+  // the first stages are issued: the rest of the setup (fragment addresses, accumulators, the epilogue's operands)
+  // and the residual / statistics loads below stay behind them
+  const GemmArgs& g = karg_after(ka);
+  __builtin_amdgcn_sched_barrier(0);
 
   // Fragment reads are inline-asm ds_read_b128 so that hipcc does not put a vmcnt(0) (for the
   // LDS-DMA still in flight into the OTHER stages) in front of them; their completion is waited
@@ -1109,18 +1149,6 @@ F5H_DEV void gemm_body(const GemmArgs& g, const int b, const int nwg, uint4* lds
 #pragma unroll
     for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int nk = g.K / BKE;
-  if constexpr (CHAIN) {
-    // phase chain: the weight panels of the first stages (no producer in the launch) are in flight while the
-    // block waits for its rows; the activation panels follow the acquire. Issue order W0 .. W(NS-2), A0 ..
-    // A(NS-2): the first wait below counts activation pieces only.
-    for (int p = 0; p < NS - 1 && p < nk; ++p) stage_w(p, p * BKE);
-    chain_wait(dep, g.M, m0, BM);
-    for (int p = 0; p < NS - 1 && p < nk; ++p) stage_a(p, p * BKE);
-  } else {
-    for (int p = 0; p < NS - 1 && p < nk; ++p) stage(p, p * BKE);
-  }
-  asm volatile("" ::: "memory");  // the residual loads below stay behind the stage DMA
   // EPI_RESID: the residual rows this lane's epilogue reads are fetched right behind the first
   // operand stages (so they do not delay stage 0: the first wait leaves them in flight, the second
   // retires them), and the epilogue's read-modify-write does not expose a dependent HBM/MALL round
@@ -1167,7 +1195,7 @@ F5H_DEV void gemm_body(const GemmArgs& g, const int b, const int nwg, uint4* lds
       wait_stages<DPS>(min(NS - 2, nk - 1 - kt));
     }
     __builtin_amdgcn_s_barrier();
-    if (kt == 0) probe_mark(g.probe, probe_t, 1);
+    if (kt == 0) probe_mark(g.probe, probe_t, 1, wg_lin);
     const uint32_t soff = (uint32_t)((kt % NS) * C::stage_bytes);
     u32x4 ar[SLABS][MT], br[SLABS][NT];
 #pragma unroll
@@ -1230,7 +1258,7 @@ F5H_DEV void gemm_body(const GemmArgs& g, const int b, const int nwg, uint4* lds
   // loaded before the loop (the residual prefetch)
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), expcnt/lgkmcnt untouched
   __syncthreads();
-  probe_mark(g.probe, probe_t, 2);
+  probe_mark(g.probe, probe_t, 2, wg_lin);
   // the fold consumer's row statistics, past the wave strips: (mean, rstd) of block row r at [2r, 2r + 2)
   float* const ln_rows = reinterpret_cast<float*>(lds) + NW * 16 * C::EPAD;
   if constexpr (LNC) {
@@ -1285,14 +1313,14 @@ F5H_DEV void gemm_body(const GemmArgs& g, const int b, const int nwg, uint4* lds
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
   }
-  probe_exit(g.probe, probe_t);
+  probe_exit(g.probe, probe_t, wg_lin);
 }
 
 template <typename TC, int EPI, int BM, int BN, int WGM, int WGN, int NS, bool FAST = false, int KB = 128, int AUX = 0,
           bool QKN = false, bool RQ = false>
 __global__ __launch_bounds__(64 * WGM * WGN, 2) void gemm_kernel(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) uint4 lds[GemmCfg<BM, BN, WGM, WGN, NS, KB>::bytes / 16];
-  gemm_body<TC, EPI, BM, BN, WGM, WGN, NS, FAST, KB, false, false, AUX, QKN, RQ>(g, blockIdx.x, gridDim.x, lds, ChainDep{});
+  gemm_body<TC, EPI, BM, BN, WGM, WGN, NS, FAST, KB, false, false, AUX, QKN, RQ>(kernarg_at<GemmArgs>(0), blockIdx.x, lds, ChainDep{});
 }
 
 // ======================================================================================
@@ -2056,8 +2084,11 @@ static void launch_8p(const GemmArgs& a, hipStream_t st) {
 }
 
 template <typename TC, int EPI, int BM, int BN, int WGM, int WGN, int NS, int KB = 128, bool QKN = false>
-static void launch_cfg(const GemmArgs& a, hipStream_t st) {
-  const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
+static hipError_t launch_cfg(const GemmArgs& a0, hipStream_t st) {
+  const int64_t tiles64 = (int64_t)((a0.M + BM - 1) / BM) * ((a0.N + BN - 1) / BN);
+  GemmArgs a = a0;  // with the launch head's fields (kernels.h gemm_head_fill)
+  if (tiles64 > (int64_t)kMagicMaxN || !gemm_head_fill(a, (int)tiles64, BN)) return hipErrorInvalidValue;
+  const int tiles = (int)tiles64;
   constexpr bool HOT = EPI == EPI_QKV || EPI == EPI_RESID || EPI == EPI_RESID16 || EPI == EPI_GELU_TANH ||
                        EPI == EPI_GELU_ERF_OP || EPI == EPI_STORE || EPI == EPI_STORE16 || EPI == EPI_INPROJ;
   if constexpr (HOT) {
@@ -2071,16 +2102,17 @@ static void launch_cfg(const GemmArgs& a, hipStream_t st) {
         if (a.store_wt) {
           hipLaunchKernelGGL((gemm_kernel<TC, EPI, BM, BN, WGM, WGN, NS, true, KB, kAuxWT, QKN>), dim3(tiles),
                              dim3(64 * WGM * WGN), 0, st, a);
-          return;
+          return hipGetLastError();
         }
       }
       hipLaunchKernelGGL((gemm_kernel<TC, EPI, BM, BN, WGM, WGN, NS, true, KB, 0, QKN>), dim3(tiles),
                          dim3(64 * WGM * WGN), 0, st, a);
-      return;
+      return hipGetLastError();
     }
   }
   hipLaunchKernelGGL((gemm_kernel<TC, EPI, BM, BN, WGM, WGN, NS, false, KB, 0, QKN>), dim3(tiles), dim3(64 * WGM * WGN),
                      0, st, a);
+  return hipGetLastError();
 }
 
 // QKV launches with qk_norm (GemmArgs q_norm_w / k_norm_w): the kernels with the norm compiled into their epilogue,
@@ -2092,15 +2124,15 @@ template <typename TC>
 static hipError_t launch_qkn(const GemmArgs& a, int cfg, hipStream_t st) {
   if constexpr (is16<TC>()) {
     switch (cfg) {
-      case 0: launch_cfg<TC, EPI_QKV, 64, 128, 2, 2, 3, 128, true>(a, st); break;
-      case 1: launch_cfg<TC, EPI_QKV, 128, 128, 2, 2, 2, 128, true>(a, st); break;
-      case 5: launch_cfg<TC, EPI_QKV, 192, 128, 2, 2, 2, 128, true>(a, st); break;
+      case 0: return launch_cfg<TC, EPI_QKV, 64, 128, 2, 2, 3, 128, true>(a, st);
+      case 1: return launch_cfg<TC, EPI_QKV, 128, 128, 2, 2, 2, 128, true>(a, st);
+      case 5: return launch_cfg<TC, EPI_QKV, 192, 128, 2, 2, 2, 128, true>(a, st);
       case 11: launch_pp<TC, EPI_QKV, 256, 256, 1, 4, 1, 3, true>(a, st); break;
       default: return hipErrorInvalidValue;
     }
   } else {  // the fp32 parity mode always uses cfg 0
     if (cfg != 0) return hipErrorInvalidValue;
-    launch_cfg<TC, EPI_QKV, 64, 128, 2, 2, 3, 128, true>(a, st);
+    return launch_cfg<TC, EPI_QKV, 64, 128, 2, 2, 3, 128, true>(a, st);
   }
   return hipGetLastError();
 }
@@ -2111,9 +2143,12 @@ hipError_t gemm_launch_rq_bf16(const GemmArgs& a, hipStream_t st);
 hipError_t gemm_launch_rq_f16(const GemmArgs& a, hipStream_t st);
 hipError_t gemm_launch_rq_f32(const GemmArgs& a, hipStream_t st);
 template <typename TC>
-static hipError_t launch_rq(const GemmArgs& a, hipStream_t st) {
+static hipError_t launch_rq(const GemmArgs& a0, hipStream_t st) {
   constexpr int BM = is16<TC>() ? 128 : 64, NS = is16<TC>() ? 2 : 3;
-  const int tiles = ((a.M + BM - 1) / BM) * ((a.N + 127) / 128);
+  const int64_t tiles64 = (int64_t)((a0.M + BM - 1) / BM) * ((a0.N + 127) / 128);
+  GemmArgs a = a0;  // with the launch head's fields
+  if (tiles64 > (int64_t)kMagicMaxN || !gemm_head_fill(a, (int)tiles64, 128)) return hipErrorInvalidValue;
+  const int tiles = (int)tiles64;
   if (a.q_norm_w)
     hipLaunchKernelGGL((gemm_kernel<TC, EPI_QKV, BM, 128, 2, 2, NS, false, 128, 0, true, true>), dim3(tiles), dim3(256), 0,
                        st, a);
@@ -2185,9 +2220,9 @@ static hipError_t launch_t(const GemmArgs& a, hipStream_t st) {
     }
   }
   switch (cfg) {
-    case 0: launch_cfg<TC, EPI, 64, 128, 2, 2, 3>(a, st); break;
-    case 1: launch_cfg<TC, EPI, 128, 128, 2, 2, 2>(a, st); break;
-    case 5: launch_cfg<TC, EPI, 192, 128, 2, 2, 2>(a, st); break;
+    case 0: return launch_cfg<TC, EPI, 64, 128, 2, 2, 3>(a, st);
+    case 1: return launch_cfg<TC, EPI, 128, 128, 2, 2, 2>(a, st);
+    case 5: return launch_cfg<TC, EPI, 192, 128, 2, 2, 2>(a, st);
     default:
       if constexpr (is16<TC>()) {
         if (a.K % 64) return hipErrorInvalidValue;  // whole K64 tiles

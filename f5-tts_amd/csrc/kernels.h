@@ -43,21 +43,29 @@ struct DevProbe {
 };
 constexpr int kTimelineWG = 8192;  // workgroups recorded per timeline
 
-// Layout: a kernel argument of every GEMM launch. Its 4-byte fields sit where alignment padding would otherwise be
-// (k_split, store_wt, qk_norm_eps away from the fields they go with), so that the struct stays 304 bytes: 24 bytes
-// more moved the hidden grid-size argument the kernels read at entry onto another cache line of the kernarg segment
-// and measured C2 -0.4 % with unchanged kernel code.
+// Layout: a kernel argument of every GEMM launch, 304 bytes: 24 bytes more moved the hidden grid-size argument onto
+// another cache line of the kernarg segment and measured C2 -0.4 % with unchanged kernel code.
+// The first 64 bytes are the hot line: everything gemm_kernel reads on its way to the first operand DMA, fetched as one
+// batch of scalar loads at entry (gemm_impl.h gemm_body; DESIGN.md §3 'Launch head'). The head_* fields are filled by
+// the launchers from the others (gemm_head_fill below); callers leave them alone. lda / ldw / ld_add / dual_rows are
+// 32-bit to make room for them; the 4-byte fields store_wt and qk_norm_eps sit where alignment padding would
+// otherwise be, away from the fields they go with.
 struct GemmArgs {
-  const void* A; int64_t lda;      // [M,K] row-major, TA elements
-  const void* W; int64_t ldw;      // [Npad,K] row-major, operand elements (rows padded to 128)
+  const void* A;                   // [M,K] row-major, TA elements, row stride lda
+  const void* W;                   // [Npad,K] row-major, operand elements (rows padded to 128), row stride ldw
+  const void* A2;                  // A columns [k_split, K) come from A2 (same lda), e.g. cat(x, skip)
+  int lda, ldw;
   int M, N, K;                     // K: multiple of 64 (bf16) / 32 (fp32)
-  int k_split;                     // with A2 (below)
+  int k_split;                     // with A2
+  unsigned head_flags;             // kHeadProbe | kHeadLive (probe.slots / live_len non-null) | div shift << 8
+  int head_nwg, head_ntn;          // the launch's workgroups and column tiles
+  unsigned head_ntn_mul;           // bid / head_ntn as a multiply and shift (MagicDiv below)
   const float* bias;               // [N] or null
   void* C; int64_t ldc;            // output
   const float* gate;               // EPI_RESID: [N] or null (=1)
   const uint8_t* rowkeep;          // [M] or null (=1)
-  const float* add; int64_t ld_add;  // EPI_INPROJ addend
-  int64_t dual_rows;               // EPI_INPROJ: second output at row m + dual_rows (0 = none)
+  const float* add; int ld_add;    // EPI_INPROJ addend
+  int dual_rows;                   // EPI_INPROJ: second output at row m + dual_rows (0 = none)
   // EPI_QKV
   const float2* rope;              // [L][32] (cos, sin)
   int seq_len;                     // L: rows per sequence
@@ -68,7 +76,6 @@ struct GemmArgs {
   float qk_norm_eps;               // qk_norm (below)
   DevProbe probe;                  // in-kernel launch timing (null slots: off)
   const void* resid;               // EPI_RESID / EPI_RESID16 residual input (null: C)
-  const void* A2;                  // A columns [k_split, K) come from A2 (same lda), e.g. cat(x, skip)
   const float* q_norm_w;           // qk_norm (below)
   // EPI_RESID / EPI_RESID16 with rowkeep: the live rows of sequence s are [s*live_seq, s*live_seq +
   // live_len[s]); a tile with no live row skips its K loop and epilogue (its rows keep the residual, as
@@ -120,6 +127,39 @@ static_assert(sizeof(GemmArgs) == 304, "GemmArgs: keep the kernel argument's siz
 static_assert(offsetof(GemmArgs, qkv_dst_len) == offsetof(GemmArgs, ln_nparts) + 4 &&
                   offsetof(GemmArgs, ln_u) == offsetof(GemmArgs, ln_nparts) + 8,
               "GemmArgs: qkv_dst_len fills the padding behind ln_nparts");
+static_assert(offsetof(GemmArgs, bias) == 64, "GemmArgs: the hot line is the first 64 bytes");
+
+// n / d without a division (the launch heads' tile indices): q = (mulhi(n, mul) + n) >> shift with shift =
+// ceil(log2 d) and mul = floor(2^(32 + shift) / d) + 1 - 2^32, the round-up method, exact for every 32-bit n; the
+// sum must not carry, so n < 2^31. The launchers use it for n < kMagicMaxN and 1 <= d <= kMagicMaxD and refuse
+// larger grids (tests/test_launch_head_div.py walks that whole range against / and %).
+constexpr unsigned kMagicMaxN = 1u << 20, kMagicMaxD = 1u << 11;
+struct MagicDiv {
+  unsigned mul, shift;
+};
+__host__ __device__ inline MagicDiv magic_div_make(unsigned d) {
+  unsigned s = 0;
+  while ((1ull << s) < d) ++s;
+  return MagicDiv{(unsigned)(((1ull << (32 + s)) / d) + 1ull - (1ull << 32)), s};
+}
+__host__ __device__ inline unsigned magic_div(unsigned n, unsigned mul, unsigned shift) {
+  return ((unsigned)(((unsigned long long)n * mul) >> 32) + n) >> shift;
+}
+
+// GemmArgs::head_flags: what the launch head must look at besides the hot line
+constexpr unsigned kHeadProbe = 1u, kHeadLive = 2u, kHeadShift = 8;
+// Fill the head_* fields for a launch of nwg workgroups over BN-column tiles (the launchers; chain.hip per phase).
+// False: the grid is outside the multiply-shift division's range.
+inline bool gemm_head_fill(GemmArgs& g, int nwg, int BN) {
+  const int ntn = (g.N + BN - 1) / BN;
+  if (nwg <= 0 || ntn <= 0 || (unsigned)nwg > kMagicMaxN || (unsigned)ntn > kMagicMaxD) return false;
+  const MagicDiv md = magic_div_make((unsigned)ntn);
+  g.head_flags = (g.probe.slots ? kHeadProbe : 0u) | (g.live_len ? kHeadLive : 0u) | (md.shift << kHeadShift);
+  g.head_nwg = nwg;
+  g.head_ntn = ntn;
+  g.head_ntn_mul = md.mul;
+  return true;
+}
 
 // EPI_QKV destination panels (GemmArgs::qkv_dst_len): rows per panel, and the elements from q / k / v to the end of
 // the launch's last panel, which holds seq_len rows (the extent of the stores' buffer descriptors; rows >= M start a
@@ -167,23 +207,30 @@ int store_policy_forced();
 
 // attention: Q,K,V [S,H,L,64] operand dtype; O [S,L,H*64] operand dtype. The softmax scale is 1/sqrt(64) (kAttnScale).
 // Layout: a kernel argument of every attention launch, held at 120 bytes (the size it had before kv_start2 / kv_len2:
-// kv_start2 sits in the padding behind L, o_split beside prescaled, and the scale became a constant) -- 8 bytes more
-// move the hidden kernel arguments, which measured C2 +0.4 % with the default kernels' code unchanged (as GemmArgs'
-// layout note; DESIGN.md §5 'Isolated batches').
+// kv_start2 sits in the padding behind L, the scale became a constant, and the three 0 / 1 switches share one word
+// with the launch head's flags) -- 8 bytes more move the hidden kernel arguments, which measured C2 +0.4 % with the
+// default kernels' code unchanged (as GemmArgs' layout note; DESIGN.md §5 'Isolated batches').
+// The first 64 bytes are the hot line: everything attn16_kernel reads on its way to the first K/V DMA, fetched as one
+// batch of scalar loads at entry (DESIGN.md §3 'Launch head'). The grid's extents follow from it (query blocks of
+// 256 rows of L, S * H (sequence, head) pairs). The head_* fields are filled by `attention` (attn_head_fill below);
+// callers leave them alone.
 constexpr float kAttnScale = 0.125f;
 struct AttnArgs {
   const void* q; const void* k; const void* v; void* o;
   int S, H, L;
-  int kv_start2;          // first row of the second key range (with kv_len2, below; in the padding behind L)
+  int kv_start2;          // first row of the second key range (with kv_len2, below)
+  unsigned prescaled : 1;   // q already carries kAttnScale*log2(e): scores are in log2 units
+  unsigned force_safe : 1;  // test hook: every workgroup reruns its key loop in the lazy-max form (attention.hip)
+  unsigned store_wt : 1;    // store policy: 1 = O is stored write-through (16-bit kernel), 0 = plain; attention_store_wt
+  // kAttnHead* (kv_len / q_len / kv_len2 / probe.slots non-null) | shift of id / nqb << 4 | shift of bh / H << 9
+  unsigned head_flags : 29;
+  unsigned head_nqb_mul, head_h_mul;  // id / nqb and bh / H as multiplies and shifts (MagicDiv above)
+  int o_split;            // split output (below)
   const int32_t* kv_len;  // [S] or null: keys [kv_len[s], L) masked
   // [S] or null: query rows [q_len[s], L) are dead (their output is masked to 0 after to_out,
   // modules.py:551-553): query blocks wholly past q_len[s] exit at entry and leave O unwritten
   const int32_t* q_len;
-  int prescaled;          // q already carries kAttnScale*log2(e): scores are in log2 units
-  int o_split;            // split output (below)
   DevProbe probe;         // in-kernel launch timing (null slots: off)
-  int force_safe;         // test hook: every workgroup reruns its key loop in the lazy-max form (attention.hip)
-  int store_wt;           // store policy: 1 = O is stored write-through (16-bit kernel), 0 = plain; attention_store_wt
   // Split output (MMDiT joint attention; 0 = none): with 0 < o_split < L, row r < o_split of sequence s goes to
   // o [S, o_split, H*64] and row r >= o_split to o2 [S, L - o_split, H*64] row r - o_split. Only the output
   // addressing changes (the Q load, the K/V ring and the softmax see one sequence of L rows). (o_split: above)
@@ -206,6 +253,22 @@ struct AttnArgs {
 };
 constexpr int kAttnRagged = -1;
 static_assert(sizeof(AttnArgs) == 120, "AttnArgs: keep the kernel argument's size (see the layout note)");
+static_assert(offsetof(AttnArgs, kv_len) == 64, "AttnArgs: the hot line is the first 64 bytes");
+constexpr unsigned kAttnHeadKv = 1u, kAttnHeadQ = 2u, kAttnHeadKv2 = 4u, kAttnHeadProbe = 8u;
+constexpr unsigned kAttnHeadShiftQb = 4, kAttnHeadShiftH = 9;
+// Fill the head_* fields of a 16-bit attention launch (query blocks of qrows rows). False: the grid is outside the
+// multiply-shift division's range.
+inline bool attn_head_fill(AttnArgs& a, int qrows) {
+  const int64_t nqb = ((int64_t)a.L + qrows - 1) / qrows, nwg = nqb * a.S * a.H;
+  if (nqb <= 0 || nwg <= 0 || nwg > (int64_t)kMagicMaxN || nqb > (int64_t)kMagicMaxD || a.H > (int)kMagicMaxD)
+    return false;
+  const MagicDiv dq = magic_div_make((unsigned)nqb), dh = magic_div_make((unsigned)a.H);
+  a.head_flags = (a.kv_len ? kAttnHeadKv : 0u) | (a.q_len ? kAttnHeadQ : 0u) | (a.kv_len2 ? kAttnHeadKv2 : 0u) |
+                 (a.probe.slots ? kAttnHeadProbe : 0u) | (dq.shift << kAttnHeadShiftQb) | (dh.shift << kAttnHeadShiftH);
+  a.head_nqb_mul = dq.mul;
+  a.head_h_mul = dh.mul;
+  return true;
+}
 hipError_t attention(int compute, const AttnArgs& a, hipStream_t st);
 int attention_store_wt(int compute, const AttnArgs& a, int want);  // as gemm_store_wt
 // test hook (f5h_attn_force_safe): 1 = every later 16-bit attention launch takes the SAFE rerun

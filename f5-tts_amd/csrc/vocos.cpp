@@ -253,7 +253,7 @@ void vlayout(const f5h_vocos* v, VWS& ws, VBufs& b, int B, int T) {
 GemmArgs vg(const void* A, int64_t lda, const VLin& W, int M, void* C, int64_t ldc) {
   GemmArgs g{};
   g.A = A;
-  g.lda = lda;
+  g.lda = (int)lda;
   g.W = W.w;
   g.ldw = W.K;
   g.M = M;

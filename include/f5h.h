@@ -567,6 +567,12 @@ int f5h_attn_force_safe(int32_t on);
  * rows [s*live_seq, (s+1)*live_seq) and its first live_len[s] rows are live; 0 if every row is padding.
  * The device kernels run the same function (kernels.h tile_live_rows). */
 int f5h_debug_tile_live(const int32_t* live_len, int32_t live_seq, int32_t M, int32_t m0, int32_t BM);
+/* Test hook (host only, no device needed): the multiply-shift division of the kernels' launch heads (kernels.h
+ * magic_div_make / magic_div, which turn a workgroup id into tile indices) against `/` and `%`: for every divisor d
+ * in [d_lo, d_hi] and every numerator n in [0, n_end), counts the (n, d) whose quotient or remainder differs and
+ * returns the count (0: exact over the whole range), or -1 for a bad range. limits (or null): receives the ranges
+ * the launchers allow, {largest numerator + 1, largest divisor}. */
+int64_t f5h_debug_magic_div_sweep(uint32_t n_end, uint32_t d_lo, uint32_t d_hi, uint32_t* limits);
 
 /* ---------------------------------------------------------------------------------------
  * Vocos decoder (mel -> waveform), SURVEY §8(f1): the step after the CFM path, replacing
