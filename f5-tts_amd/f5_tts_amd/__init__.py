@@ -8,6 +8,15 @@ the reference's Python surface (`f5_tts.model.{CFM, DiT, UNetT}`, `f5_tts.api.F5
 __version__ = "0.1.0"
 
 
+def __getattr__(name):
+    # `from f5_tts_amd import BatchingSynthesizer` without importing torch with the bare package
+    if name == "BatchingSynthesizer":
+        from .serve import BatchingSynthesizer
+
+        return BatchingSynthesizer
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 def release_memory() -> int:
     """Wait for queued engine / Vocos / log-mel releases, then return the device pool's unused memory to the
     system (f5h_release_pending(2); waits for the device). Returns the releases still pending (0)."""

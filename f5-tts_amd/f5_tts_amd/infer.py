@@ -391,6 +391,41 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
         yield None, target_sample_rate, None
 
 
+def prepare_prompt(ref_audio, ref_text, target_rms=target_rms):
+    """The per-prompt intake of `infer_batch` (and of `serve.BatchingSynthesizer`): `ref_audio` a WAV path or an
+    `(audio [C, n] tensor, sr)` tuple -> mono, RMS boost to `target_rms` when quieter, resample to 24 kHz; a space
+    after a `ref_text` ending in a single-byte character. Returns `(wave [n] float32, rms before the boost (0-dim),
+    ref_text, ref)` with `ref` the prompt's mel frames. Host work only."""
+    audio, sr = load_audio(ref_audio) if isinstance(ref_audio, str) else ref_audio
+    if audio.ndim == 1:
+        audio = audio[None]
+    if audio.shape[0] > 1:
+        audio = torch.mean(audio, dim=0, keepdim=True)
+    rms = torch.sqrt(torch.mean(torch.square(audio)))
+    if rms < target_rms:
+        audio = audio * target_rms / rms
+    if sr != target_sample_rate:
+        audio = resample(audio, sr, target_sample_rate)
+    if len(ref_text[-1].encode("utf-8")) == 1:
+        ref_text = ref_text + " "
+    ref = 1 + audio.shape[-1] // hop_length  # the prompt's mel frames (torch.stft center=True)
+    return audio[0], rms, ref_text, ref
+
+
+def prepare_item(prompt, gen_text, speed=speed, what="item", fix_duration=None):
+    """The per-utterance intake on a prepared prompt: the tokens of `ref_text + gen_text` and the duration rule,
+    total frames = ref + int(ref / len(ref_text bytes) * len(gen_text bytes) / speed), or `fix_duration` seconds in
+    all when given. Nothing to generate (total <= ref) raises ValueError naming `what`."""
+    audio, rms, ref_text, ref = prompt
+    if fix_duration is not None:
+        total = int(fix_duration * target_sample_rate / hop_length)
+    else:
+        total = ref + int(ref / len(ref_text.encode("utf-8")) * len(gen_text.encode("utf-8")) / speed)
+    if total <= ref:
+        raise ValueError(f"{what}: nothing to generate ({len(gen_text.encode('utf-8'))} bytes of gen_text)")
+    return dict(audio=audio, rms=rms, text=convert_char_to_pinyin([ref_text + gen_text])[0], ref=ref, total=total)
+
+
 def infer_batch(items, model_obj, vocoder, *, nfe_step=nfe_step, cfg_strength=cfg_strength,
                 sway_sampling_coef=sway_sampling_coef, speed=1.0, seed=None, target_rms=target_rms, max_batch=32,
                 isolate=False, ragged=False):
@@ -426,25 +461,8 @@ def infer_batch(items, model_obj, vocoder, *, nfe_step=nfe_step, cfg_strength=cf
     prep = []
     for k, item in enumerate(items):
         ref_audio, ref_text, gen_text = item[:3]
-        speed_k = overs[k].get("speed", speed)
-        audio, sr = load_audio(ref_audio) if isinstance(ref_audio, str) else ref_audio
-        if audio.ndim == 1:
-            audio = audio[None]
-        if audio.shape[0] > 1:
-            audio = torch.mean(audio, dim=0, keepdim=True)
-        rms = torch.sqrt(torch.mean(torch.square(audio)))
-        if rms < target_rms:
-            audio = audio * target_rms / rms
-        if sr != target_sample_rate:
-            audio = resample(audio, sr, target_sample_rate)
-        if len(ref_text[-1].encode("utf-8")) == 1:
-            ref_text = ref_text + " "
-        ref = 1 + audio.shape[-1] // hop_length  # the prompt's mel frames (torch.stft center=True)
-        total = ref + int(ref / len(ref_text.encode("utf-8")) * len(gen_text.encode("utf-8")) / speed_k)
-        if total <= ref:
-            raise ValueError(f"item {k}: nothing to generate ({len(gen_text.encode('utf-8'))} bytes of gen_text)")
-        prep.append(dict(audio=audio[0], rms=rms, text=convert_char_to_pinyin([ref_text + gen_text])[0], ref=ref,
-                         total=total))
+        prep.append(prepare_item(prepare_prompt(ref_audio, ref_text, target_rms), gen_text,
+                                 overs[k].get("speed", speed), f"item {k}"))
     waves = [None] * len(prep)
     with torch.inference_mode():
         if ragged:  # no pad frames to limit: batches of max_batch in input order

@@ -139,7 +139,8 @@ class CFM(nn.Module):
     def sample(self, cond, text, duration, *, lens=None, steps=32, cfg_strength=1.0, sway_sampling_coef=None,
                seed: int | None = None, max_duration=65536, vocoder: Callable | None = None, use_epss=True,
                no_ref_audio=False, duplicate_test=False, t_inter=0.1, edit_mask=None, y0=None,
-               keep_trajectory: bool = True, isolate: bool = False, ragged: bool = False):
+               keep_trajectory: bool = True, isolate: bool = False, ragged: bool = False,
+               ragged_lmax: int | None = None):
         """Same arguments/returns as the reference `CFM.sample`; extra keyword `y0` supplies the
         initial noise explicitly (parity tests), `keep_trajectory=False` skips the [steps+1,...] copy.
         `isolate=True`: every utterance of a batch is sampled as if it were alone (f5h.h use_batch_mask == 2), so its
@@ -148,6 +149,10 @@ class CFM(nn.Module):
         `ragged=True` (DiT): the isolated batch computed on packed rows, without the pad frames (f5h_sample_ragged):
         the same bits as `isolate=True` below every utterance's duration and exact zeros past it, in the same shapes;
         with one utterance it is the plain call. UNetT, MMDiT and text average upsampling raise NotImplementedError.
+        `ragged_lmax` (ragged calls only, ignored otherwise): the `lmax` of `Engine.sample_ragged`, the geometry of the
+        per-utterance launches (default: the longest duration); calls with equal (B, R, lmax) replay one step graph,
+        and the results do not depend on it. A value below the longest duration raises ValueError before any device
+        work.
         `seed` also takes one entry per utterance (a list, a tuple or a CPU tensor, in every mode): utterance b's
         noise is drawn after `torch.manual_seed(seed[b])`, as its own call with that seed would draw it (a None entry
         draws without reseeding); a list of the wrong length raises ValueError before any device work. An int seeds
@@ -185,8 +190,13 @@ class CFM(nn.Module):
         # The duration rule (cfm.py:132-139) decides the padded length, which the host needs. When the
         # lengths are host values (ints, lists, CPU tensors) it is evaluated on the host and nothing waits
         # for the device, so back-to-back calls keep the GPU busy; device-resident lengths take one sync.
+        def check_lmax(dur):
+            if ragged and ragged_lmax is not None and int(ragged_lmax) < max(dur):
+                raise ValueError(f"ragged_lmax = {int(ragged_lmax)} is below the longest duration ({max(dur)} frames)")
+
         dur_host = _duration_rule_on_host(text, duration, lens, batch, cond_seq_len, max_duration)
         if dur_host is not None:
+            check_lmax(dur_host)  # host lengths: refused before anything goes to the device
             lens_host = [cond_seq_len] * batch if lens is None else _host_ints(lens, batch)
             lens = _to_device(lens_host, device)
             duration = _to_device(dur_host, device)
@@ -206,6 +216,7 @@ class CFM(nn.Module):
             duration = duration.clamp(max=max_duration)
             dur_host = [int(d) for d in duration.tolist()]  # the one host sync of this path
         max_duration = max(dur_host)
+        check_lmax(dur_host)
         if edit_mask is not None:
             cond_mask = lens_to_mask(lens) & edit_mask
         else:  # == F.pad(lens_to_mask(lens), ...) below: max_duration > lens.amax() by the rule above
@@ -248,7 +259,8 @@ class CFM(nn.Module):
             pack = lambda x: torch.cat([x[b, :d] for b, d in enumerate(dur_host)], dim=0)  # noqa: E731
             out_p, traj_p = eng.sample_ragged(pack(cond.float()), pack(cond_mask), text, dur_host, pack(y0.float()),
                                               t_host, float(cfg_strength), keep_trajectory=keep_trajectory,
-                                              method=self.ode_method)
+                                              method=self.ode_method,
+                                              **({} if ragged_lmax is None else {"lmax": int(ragged_lmax)}))
             out, traj = _unpack_ragged(out_p, traj_p, dur_host, max_duration)
         else:
             out, traj = eng.sample(cond.float(), cond_mask, text, duration, y0.float(), t_host, float(cfg_strength),
