@@ -10,6 +10,7 @@
 //                     f5h_set_chain, f5h_chain_stats, f5h_chain_debug_spin_limit
 //   engine_ctl.cpp    the error string (g_err, fail), switches, statistics, probes, f5h_*_force_*
 //   engine_ops.cpp    op-level test hooks (f5h_op_*, f5h_debug_*), OpWs, op_seg_check: never on the product path
+//   engine_ops_glue.cpp  op-level test hooks of the audio glue, prologue and ODE step kernels (no staging)
 // Everything declared here has hidden visibility: libf5h.so exports the C API only.
 #pragma once
 #include <hip/hip_runtime.h>

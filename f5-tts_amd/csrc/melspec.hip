@@ -52,6 +52,10 @@ hipError_t mel_mag(const float* spec, int64_t rows, int bins, int ld_spec, int l
   return hipGetLastError();
 }
 
+// clamp(min=1e-5) as torch computes it: a NaN stays NaN (C fmaxf would return the other operand, 1e-5, and turn a
+// corrupt bin into silence); every other value has fmaxf's bits
+F5H_DEV float clamp_floor(float x) { return x < 1e-5f ? 1e-5f : x; }
+
 // out[b][m][t] = log(max(mel[b*T + t][m], 1e-5)): the [B, n_mels, T] layout the reference returns
 __global__ void mel_log_kernel(const float* mel, int B, int T, int n_mels, float* out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -59,7 +63,7 @@ __global__ void mel_log_kernel(const float* mel, int B, int T, int n_mels, float
   const int t = (int)(i % T);
   const int64_t bm = i / T;
   const int m = (int)(bm % n_mels), b = (int)(bm / n_mels);
-  out[i] = logf(fmaxf(mel[((int64_t)b * T + t) * n_mels + m], 1e-5f));
+  out[i] = logf(clamp_floor(mel[((int64_t)b * T + t) * n_mels + m]));
 }
 hipError_t mel_log(const float* mel, int B, int T, int n_mels, float* out, hipStream_t st) {
   const int64_t n = (int64_t)B * n_mels * T;
@@ -101,7 +105,7 @@ __global__ void mel_log_ragged_kernel(const float* mel, const int* off, int B, i
   const int64_t st = i / n_mels;
   const int t = (int)(st % T_out), s = (int)(st / T_out);
   const int base = off[s];
-  out[i] = t < off[s + 1] - base ? logf(fmaxf(mel[((int64_t)base + t) * n_mels + m], 1e-5f)) : 0.f;
+  out[i] = t < off[s + 1] - base ? logf(clamp_floor(mel[((int64_t)base + t) * n_mels + m])) : 0.f;
 }
 hipError_t mel_log_ragged(const float* mel, const int32_t* off, int B, int T_out, int n_mels, float* out,
                           hipStream_t st) {

@@ -59,7 +59,10 @@ __global__ void vocos_spec_kernel(float* x, int64_t rows, int bins, int ld) {
     return;
   }
   const float2 mp = *p;
-  const float mag = fminf(expf(mp.x), 100.f);  // torch.clip(exp, max=1e2); NaN propagates as in torch
+  // torch.clip(exp, max=1e2). A comparison, not fminf: C fminf returns the non-NaN operand and would turn a NaN
+  // log-magnitude into magnitude 100; this way NaN propagates as in torch, and every other value has fminf's bits
+  const float e = expf(mp.x);
+  const float mag = e > 100.f ? 100.f : e;
   float s, c;
   sincosf(mp.y, &s, &c);
   *p = make_float2(mag * c, mag * s);

@@ -75,6 +75,26 @@ EXPORTS = (
     "f5h_op_text_upsample",
     "f5h_op_lnfold_uv",
     "f5h_op_scale_cols",
+    "f5h_op_mel_frames",
+    "f5h_op_mel_frames_ragged",
+    "f5h_op_mel_mag",
+    "f5h_op_mel_log",
+    "f5h_op_mel_log_ragged",
+    "f5h_op_vocos_imcol",
+    "f5h_op_vocos_imcol_ragged",
+    "f5h_op_vocos_spec",
+    "f5h_op_vocos_ola",
+    "f5h_op_vocos_ola_ragged",
+    "f5h_op_time_sinus",
+    "f5h_op_rope_table",
+    "f5h_op_text_embed",
+    "f5h_op_build_ct",
+    "f5h_op_pack_y",
+    "f5h_op_masks",
+    "f5h_op_final_where_out",
+    "f5h_op_copy_pred",
+    "f5h_op_cfg_euler",
+    "f5h_op_cfg_rk",
     "f5h_gemm_force_config",
     "f5h_attn_force_safe",
     "f5h_debug_tile_live",
@@ -179,6 +199,22 @@ class RaggedArgs(ctypes.Structure):
         ("duration", ctypes.c_void_p), ("y0", ctypes.c_void_p), ("t_grid", ctypes.c_void_p),
         ("cfg_strength", ctypes.c_float),
         ("out", ctypes.c_void_p), ("trajectory", ctypes.c_void_p),
+    ]
+
+
+class OpStepArgs(ctypes.Structure):
+    """f5h_op_step_args (f5h_op_cfg_euler / f5h_op_cfg_rk)"""
+    _fields_ = [
+        ("compute", ctypes.c_int32), ("method", ctypes.c_int32),
+        ("B", ctypes.c_int32), ("N", ctypes.c_int32), ("mel", ctypes.c_int32), ("use_cfg", ctypes.c_int32),
+        ("cfg", ctypes.c_float), ("dt", ctypes.c_float),
+        ("y", ctypes.c_void_p), ("p", ctypes.c_void_p),
+        ("p_seq_stride", ctypes.c_int64), ("p_ld", ctypes.c_int64),
+        ("p_row_off", ctypes.c_int32), ("nfe", ctypes.c_int32),
+        ("ypad", ctypes.c_void_p), ("traj", ctypes.c_void_p), ("kbuf", ctypes.c_void_p),
+        ("kstep", ctypes.c_void_p), ("tgrid", ctypes.c_void_p), ("trajp", ctypes.c_void_p),
+        ("next_src", ctypes.c_void_p), ("next_stride", ctypes.c_int64), ("next_n", ctypes.c_int32),
+        ("next_dst", ctypes.c_void_p), ("arrive", ctypes.c_void_p), ("tick", ctypes.c_void_p),
     ]
 
 
@@ -351,6 +387,30 @@ def lib():
         L.f5h_op_conv_pos_ragged.restype = ctypes.c_int
         L.f5h_op_grn_ragged.argtypes = [vp, i32, i32, i32, i32, i32, pi32, vp, vp, vp, vp, vp, sz]
         L.f5h_op_grn_ragged.restype = ctypes.c_int
+    if hasattr(L, "f5h_op_cfg_euler"):  # absent from an older build (has_glue_ops)
+        for name, args in (
+                ("f5h_op_mel_frames", [vp, i32, i32, i32, i32, vp, vp]),
+                ("f5h_op_mel_frames_ragged", [vp, i32, i32, i32, i32, vp, i64, vp, vp, vp]),
+                ("f5h_op_mel_mag", [vp, i64, i32, i32, i32, vp, vp]),
+                ("f5h_op_mel_log", [vp, i32, i32, i32, vp, vp]),
+                ("f5h_op_mel_log_ragged", [vp, i32, i32, i32, vp, vp, vp]),
+                ("f5h_op_vocos_imcol", [vp, i32, i32, i32, i32, i32, vp, vp]),
+                ("f5h_op_vocos_imcol_ragged", [vp, i32, i32, i32, i32, i32, vp, i64, i64, i64, vp, vp, vp]),
+                ("f5h_op_vocos_spec", [vp, i64, i32, i32, vp]),
+                ("f5h_op_vocos_ola", [vp, i32, i32, i32, i32, vp, vp, vp]),
+                ("f5h_op_vocos_ola_ragged", [vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+                ("f5h_op_time_sinus", [vp, i32, i32, vp, vp]),
+                ("f5h_op_rope_table", [vp, i32, vp]),
+                ("f5h_op_text_embed", [vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+                ("f5h_op_build_ct", [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+                ("f5h_op_pack_y", [vp, i32, i32, i32, vp, vp]),
+                ("f5h_op_masks", [vp, i32, i32, i32, i32, i32, vp, vp]),
+                ("f5h_op_final_where_out", [vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+                ("f5h_op_copy_pred", [vp, i32, i32, i32, i32, i64, vp, vp, vp]),
+                ("f5h_op_cfg_euler", [vp, ctypes.POINTER(OpStepArgs)]),
+                ("f5h_op_cfg_rk", [vp, ctypes.POINTER(OpStepArgs)])):
+            getattr(L, name).argtypes = args
+            getattr(L, name).restype = ctypes.c_int
     L.f5h_last_error.argtypes = []
     L.f5h_last_error.restype = ctypes.c_char_p
     L.f5h_version.argtypes = []
@@ -392,6 +452,12 @@ def has_ragged_sampler() -> bool:
     """False for an older build (F5H_LIB) without f5h_sample_ragged: such a library has no ragged sampling path
     (CFM.sample(ragged=True)), no ragged op hooks and ignores the seg_off field of the GEMM op hook."""
     return hasattr(lib(), "f5h_sample_ragged")
+
+
+def has_glue_ops() -> bool:
+    """False for an older build (F5H_LIB) without f5h_op_cfg_euler: such a library has no op hooks for the audio
+    glue, prologue and ODE step kernels."""
+    return hasattr(lib(), "f5h_op_cfg_euler")
 
 
 def check(rc: int, what: str = "f5h"):

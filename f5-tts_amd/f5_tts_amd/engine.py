@@ -848,6 +848,370 @@ def op_scale_cols(W, g, compute="bf16"):
     return out
 
 
+# ---------------------------------------------------------------- op-level helpers: audio glue, prologue, ODE step
+# One launcher call each on the caller's tensors (f5h_op_* of csrc/engine_ops_glue.cpp): no staging, so a buffer in the
+# operand dtype comes back as a torch.bfloat16 / torch.float16 tensor. Every output is a view of a buffer that starts
+# as NaN (integers: OP_FILL) and ends in OP_GUARD more such elements: an element the kernel leaves alone comes back as
+# that fill, and op_guard_intact(out) tells whether it wrote past the end.
+OP_TORCH_DTYPE = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
+OP_GUARD, OP_FILL = 256, 0x5A
+
+
+def _guarded(shape, dev, dtype=torch.float32):
+    n = 1
+    for s in shape:
+        n *= int(s)
+    fill = float("nan") if dtype.is_floating_point else OP_FILL
+    return torch.full((n + OP_GUARD,), fill, dtype=dtype, device=dev)[:n].view(*shape)
+
+
+def op_guard_intact(out) -> bool:
+    """True when the OP_GUARD elements behind an op_* output still hold their fill."""
+    tail = out._base[out.numel():]
+    return bool((torch.isnan(tail) if tail.dtype.is_floating_point else tail == OP_FILL).all())
+
+
+def _glue(name, *args):
+    if not _lib.has_glue_ops():
+        raise RuntimeError(f"the loaded libf5h.so has no {name} (an older build)")
+    _lib.check(getattr(_lib.lib(), name)(*args), name)
+
+
+def _dp(t):
+    """Device pointer of a view, also when it has no elements (the guard behind it is still there)."""
+    return t.data_ptr() or t._base.data_ptr()
+
+
+def _i32(vals, dev):
+    return torch.tensor([int(v) for v in vals], dtype=torch.int32).to(dev)
+
+
+def _offsets(lens):
+    off = [0]
+    for n in lens:
+        off.append(off[-1] + int(n))
+    return off
+
+
+def op_mel_frames(wav, n_fft, hop):
+    """wav [B, L] -> frames [B, T, n_fft], T = 1 + L // hop (mel_frames: centred, reflect-padded windows)."""
+    B, L = wav.shape
+    wav = _f32(wav)
+    out = _guarded((B, 1 + L // hop, n_fft), wav.device)
+    _glue("f5h_op_mel_frames", _lib.stream_handle(wav.device), B, L, int(n_fft), int(hop), wav.data_ptr(), _dp(out))
+    return out
+
+
+def op_mel_frames_ragged(wav, lens, n_fft, hop):
+    """wav [B, wav_st] with wave s in its first lens[s] samples (host ints) -> packed frames [sum T_s, n_fft]."""
+    B, wav_st = wav.shape
+    wav = _f32(wav)
+    lens = [int(n) for n in lens]
+    assert len(lens) == B and all(n_fft // 2 < n <= wav_st for n in lens), "every wave needs n_fft/2 < len <= stride"
+    off = _offsets(1 + n // hop for n in lens)
+    out = _guarded((off[-1], n_fft), wav.device)
+    off_d, len_d = _i32(off, wav.device), _i32(lens, wav.device)  # (held until the launch is enqueued)
+    _glue("f5h_op_mel_frames_ragged", _lib.stream_handle(wav.device), B, off[-1], int(n_fft), int(hop),
+          wav.data_ptr(), wav_st, off_d.data_ptr(), len_d.data_ptr(), _dp(out))
+    return out
+
+
+def op_mel_mag(spec, bins, ld_mag):
+    """spec [rows, ld_spec] interleaved (re, im) -> mag [rows, ld_mag] (mel_mag)."""
+    rows, ld_spec = spec.shape
+    spec = _f32(spec)
+    out = _guarded((rows, ld_mag), spec.device)
+    _glue("f5h_op_mel_mag", _lib.stream_handle(spec.device), rows, int(bins), ld_spec, int(ld_mag), spec.data_ptr(),
+          _dp(out))
+    return out
+
+
+def op_mel_log(mel, B, T):
+    """mel [B * T, n_mels] -> log(max(mel, 1e-5)) as [B, n_mels, T] (mel_log)."""
+    mel = _f32(mel)
+    assert mel.shape[0] == B * T
+    out = _guarded((B, mel.shape[1], T), mel.device)
+    _glue("f5h_op_mel_log", _lib.stream_handle(mel.device), int(B), int(T), mel.shape[1], mel.data_ptr(), _dp(out))
+    return out
+
+
+def op_mel_log_ragged(mel, frames, T_out):
+    """mel [sum frames, n_mels] packed, frames: host ints T_s -> [B, T_out, n_mels], zeros past T_s (mel_log_ragged)."""
+    mel = _f32(mel)
+    off = _offsets(frames)
+    assert off[-1] == mel.shape[0] and all(1 <= t <= T_out for t in frames)
+    out = _guarded((len(frames), T_out, mel.shape[1]), mel.device)
+    off_d = _i32(off, mel.device)
+    _glue("f5h_op_mel_log_ragged", _lib.stream_handle(mel.device), len(frames), int(T_out), mel.shape[1],
+          mel.data_ptr(), off_d.data_ptr(), _dp(out))
+    return out
+
+
+def op_vocos_im2col(mel, Kp, compute="fp32"):
+    """mel [B, C, T] -> the embed conv's im2col [B * T, Kp] in the operand dtype (vocos_im2col)."""
+    B, C, T = mel.shape
+    mel = _f32(mel)
+    out = _guarded((B * T, Kp), mel.device, OP_TORCH_DTYPE[compute])
+    _glue("f5h_op_vocos_imcol", _lib.stream_handle(mel.device), _lib.COMPUTE[compute], B, T, C, int(Kp),
+          mel.data_ptr(), _dp(out))
+    return out
+
+
+def op_vocos_im2col_ragged(src, layout, starts, lens, Kp, compute="fp32"):
+    """src: "BNC" [B, N, C] or "BCT" [B, C, T]; utterance s = frames [starts[s], starts[s] + lens[s]) of row s (host
+    ints) -> packed im2col rows [sum lens, Kp] (vocos_im2col_ragged), read in place through element strides."""
+    src = _f32(src)
+    B = src.shape[0]
+    if layout == "BNC":
+        n_frames, C = src.shape[1], src.shape[2]
+        strides = (n_frames * C, C, 1)
+    else:
+        assert layout == "BCT"
+        C, n_frames = src.shape[1], src.shape[2]
+        strides = (C * n_frames, 1, n_frames)
+    assert len(starts) == len(lens) == B
+    assert all(s >= 0 and n >= 1 and s + n <= n_frames for s, n in zip(starts, lens))
+    off = _offsets(lens)
+    out = _guarded((off[-1], Kp), src.device, OP_TORCH_DTYPE[compute])
+    off_d, start_d = _i32(off, src.device), _i32(starts, src.device)  # (held until the launch is enqueued)
+    _glue("f5h_op_vocos_imcol_ragged", _lib.stream_handle(src.device), _lib.COMPUTE[compute], B, off[-1], C, int(Kp),
+          src.data_ptr(), *strides, off_d.data_ptr(), start_d.data_ptr(), _dp(out))
+    return out
+
+
+def op_vocos_spec(x, bins):
+    """x [rows, ld] of (log-magnitude, phase) pairs -> (re, im) pairs, pad columns zero (vocos_spec; on a copy)."""
+    rows, ld = x.shape
+    out = _guarded((rows, ld), x.device)
+    out.copy_(x)
+    _glue("f5h_op_vocos_spec", _lib.stream_handle(x.device), rows, int(bins), ld, _dp(out))
+    return out
+
+
+def op_vocos_ola(frames, win, B, T, hop):
+    """frames [B * T, n_fft] windowed, win [n_fft] -> y [B, (T - 1) * hop] (vocos_ola)."""
+    frames, win = _f32(frames), _f32(win, frames.device)
+    n_fft = frames.shape[1]
+    assert frames.shape[0] == B * T and win.numel() == n_fft
+    out = _guarded((B, (T - 1) * hop), frames.device)
+    _glue("f5h_op_vocos_ola", _lib.stream_handle(frames.device), int(B), int(T), n_fft, int(hop), frames.data_ptr(),
+          win.data_ptr(), _dp(out))
+    return out
+
+
+def op_vocos_ola_ragged(frames, win, lens, hop):
+    """frames [sum lens, n_fft] packed -> y [(sum lens - B) * hop] packed (vocos_ola_ragged)."""
+    frames, win = _f32(frames), _f32(win, frames.device)
+    n_fft = frames.shape[1]
+    off = _offsets(lens)
+    assert off[-1] == frames.shape[0] and all(n >= 1 for n in lens) and win.numel() == n_fft
+    out = _guarded(((off[-1] - len(lens)) * hop,), frames.device)
+    off_d = _i32(off, frames.device)
+    _glue("f5h_op_vocos_ola_ragged", _lib.stream_handle(frames.device), len(lens), off[-1], n_fft, int(hop),
+          frames.data_ptr(), win.data_ptr(), off_d.data_ptr(), _dp(out))
+    return out
+
+
+def op_time_sinus(t, dev=False, device="cuda:0"):
+    """t: n time values -> [n, 256] sinusoidal embedding. dev=False: time_sinus (host values as kernel arguments);
+    dev=True: time_sinus_dev (the values read from device memory)."""
+    vals = [float(v) for v in (t.reshape(-1).tolist() if torch.is_tensor(t) else t)]
+    n = len(vals)
+    out = _guarded((n, 256), device)
+    if dev:
+        tg = torch.tensor(vals + [0.0], dtype=torch.float32).to(device)  # (one spare value: never a null pointer)
+        _glue("f5h_op_time_sinus", _lib.stream_handle(device), 1, n, tg.data_ptr(), _dp(out))
+    else:
+        arr = (ctypes.c_float * (n + 1))(*vals)
+        _glue("f5h_op_time_sinus", _lib.stream_handle(device), 0, n, ctypes.addressof(arr), _dp(out))
+    return out
+
+
+def op_rope_table(L, device="cuda:0"):
+    """[L, 32, 2] (cos, sin) rotary table (rope_table)."""
+    out = _guarded((L, 32, 2), device)
+    _glue("f5h_op_rope_table", _lib.stream_handle(device), int(L), _dp(out))
+    return out
+
+
+def op_text_embed(text, table, N, seq_len=None, freqs=None, freq_rows=0, mask_padding=False, seg_lens=None):
+    """text_embed alone: text [B, nt] int64 (-1 = filler), table [V, td], freqs [rows, td] or None. Returns (out_c,
+    out_u [B, N, td], keep [2, B, N] bytes). seg_lens (host ints): the ragged form, N is ignored and the outputs are
+    packed rows [sum seg_lens, td], keep [2, R]."""
+    dev = text.device
+    B, nt = text.shape
+    text = text.to(torch.int64).contiguous()
+    table, freqs = _f32(table, dev), _f32(freqs, dev)
+    V, td = table.shape
+    assert int(text.min()) >= -1 and int(text.max()) + 1 < V, "token ids must index the table"
+    sl = off = None
+    if seg_lens is not None:
+        assert seq_len is None and len(seg_lens) == B and all(n >= 1 for n in seg_lens)
+        offs = _offsets(seg_lens)
+        N, rows, longest = offs[-1], offs[-1], max(seg_lens)
+        off = _i32(offs, dev)
+    else:
+        rows, longest = B * N, N
+        if seq_len is not None:
+            sl = _i32(seq_len, dev)
+            assert sl.numel() == B
+    if freqs is not None:
+        assert freqs.shape[1] == td and freqs.shape[0] >= (freq_rows if freq_rows else longest)
+    shape = (rows, td) if seg_lens is not None else (B, N, td)
+    out_c, out_u = _guarded(shape, dev), _guarded(shape, dev)
+    keep = _guarded((2, rows) if seg_lens is not None else (2, B, N), dev, torch.uint8)
+    _glue("f5h_op_text_embed", _lib.stream_handle(dev), B, nt, int(N), td, text.data_ptr(), _lib.ptr(sl),
+          table.data_ptr(), _lib.ptr(freqs), int(freq_rows), int(bool(mask_padding)), _dp(out_c), _dp(out_u),
+          _dp(keep), _lib.ptr(off))
+    return out_c, out_u, keep
+
+
+def op_build_ct(cond, cond_mask, text_c, text_u, S, drop_audio=False, drop_text=False, compute="fp32"):
+    """build_ct alone: cond [B, N, 100], cond_mask [B, N], text_c / text_u [B, N, td] -> [S * N, 128 + roundup(td,
+    64)] in the operand dtype."""
+    B, N, mel = cond.shape
+    assert mel == 100
+    dev = cond.device
+    cond, text_c, text_u = _f32(cond), _f32(text_c, dev), _f32(text_u, dev)
+    td = text_c.shape[2]
+    assert text_c.shape == text_u.shape == (B, N, td)
+    cm = _u8(cond_mask, dev)
+    out = _guarded((S * N, 128 + (td + 63) // 64 * 64), dev, OP_TORCH_DTYPE[compute])
+    _glue("f5h_op_build_ct", _lib.stream_handle(dev), _lib.COMPUTE[compute], B, N, td, int(S), int(bool(drop_audio)),
+          int(bool(drop_text)), cond.data_ptr(), cm.data_ptr(), text_c.data_ptr(), text_u.data_ptr(), _dp(out))
+    return out
+
+
+def op_pack_y(y, compute="fp32"):
+    """y [rows, mel] fp32 -> [rows, 128] in the operand dtype, pad columns zero (pack_y)."""
+    rows, mel = y.shape
+    y = _f32(y)
+    out = _guarded((rows, 128), y.device, OP_TORCH_DTYPE[compute])
+    _glue("f5h_op_pack_y", _lib.stream_handle(y.device), _lib.COMPUTE[compute], rows, mel, y.data_ptr(), _dp(out))
+    return out
+
+
+MASK_KIND = {"build_rowkeep": 0, "build_kvlen": 1, "build_textkeep": 2, "build_textlen": 3}
+
+
+def op_masks(kind, src, S, L=0, off=0):
+    """The mask builders. build_rowkeep / build_kvlen: src = dur [B] int32 -> keep [S, L] bytes / kv_len [S] int32;
+    build_textkeep / build_textlen: src = text [B, nt] int64 -> keep [S, nt] bytes / len [S] int32."""
+    dev = src.device
+    k = MASK_KIND[kind]
+    if k < 2:
+        src = src.to(torch.int32).contiguous()
+        B = src.numel()
+    else:
+        src = src.to(torch.int64).contiguous()
+        B, L = src.shape
+    out = _guarded((S, L), dev, torch.uint8) if k in (0, 2) else _guarded((S,), dev, torch.int32)
+    _glue("f5h_op_masks", _lib.stream_handle(dev), k, B, int(S), int(L), int(off), src.data_ptr(), _dp(out))
+    return out
+
+
+def _fault_word(fault, dev):
+    return None if fault is None else torch.tensor([int(fault)], dtype=torch.int32).to(dev)
+
+
+def op_final_where_out(cond, cond_mask, y, fault=None):
+    """where(cond_mask, cond, y) over [B, N, mel]; fault: None (no fault word), 0 or 1 (NaN output)."""
+    B, N, mel = y.shape
+    dev = y.device
+    cond, y, cm, fw = _f32(cond, dev), _f32(y), _u8(cond_mask, dev), _fault_word(fault, dev)
+    out = _guarded((B, N, mel), dev)
+    _glue("f5h_op_final_where_out", _lib.stream_handle(dev), B, N, mel, cond.data_ptr(), cm.data_ptr(), y.data_ptr(),
+          _dp(out), _lib.ptr(fw))
+    return out
+
+
+def op_copy_pred(p, row_off, mel, fault=None):
+    """p [S, L, p_ld] -> rows [row_off, L) and columns [0, mel) of every sequence, [S, L - row_off, mel]."""
+    S, L, p_ld = p.shape
+    p, fw = _f32(p), _fault_word(fault, p.device)
+    out = _guarded((S, L - row_off, mel), p.device)
+    _glue("f5h_op_copy_pred", _lib.stream_handle(p.device), S, L, int(row_off), int(mel), p_ld, p.data_ptr(), _dp(out),
+          _lib.ptr(fw))
+    return out
+
+
+def _op_step(name, method, y, p, p_row_off, use_cfg, cfg, compute, ypad, kbuf, dt, traj, k, grid, n_count, table,
+             next_n, trajp, arrive, tick):
+    """Shared body of op_cfg_euler / op_cfg_rk: builds the side buffers, launches once, returns them all."""
+    B, N, mel = y.shape
+    dev = y.device
+    total = B * N * mel
+    y, p = _f32(y).clone(), _f32(p)
+    a = _lib.OpStepArgs()
+    a.compute, a.method, a.B, a.N, a.mel, a.use_cfg = _lib.COMPUTE[compute], method, B, N, mel, int(bool(use_cfg))
+    a.cfg = float(cfg)
+    a.y, a.p = y.data_ptr(), p.data_ptr()
+    a.p_seq_stride, a.p_ld, a.p_row_off = p.shape[1] * p.shape[2], p.shape[2], int(p_row_off)
+    assert p.shape[0] >= (2 * B if use_cfg else B) and p.shape[1] >= p_row_off + N and p.shape[2] >= mel
+    res = {"y": y}
+    if ypad is not None:
+        res["ypad"] = _guarded((B * N, 128), dev, OP_TORCH_DTYPE[ypad])
+        assert ypad == compute, "the launch writes ypad in its compute mode's operand dtype"
+        a.ypad = _dp(res["ypad"])
+    if kbuf is not None:
+        res["kbuf"] = _f32(kbuf).clone()
+        assert res["kbuf"].numel() == 3 * total
+        a.kbuf = res["kbuf"].data_ptr()
+    if k is None:  # host form (Euler)
+        a.dt = float(dt)
+        if traj:
+            res["traj"] = _guarded((B, N, mel), dev)
+            a.traj = _dp(res["traj"])
+    else:
+        steps = len(grid) - 1
+        a.nfe = int(n_count)
+        res["grid"] = torch.tensor([float(v) for v in grid], dtype=torch.float32).to(dev)
+        res["kstep"] = torch.tensor([int(k), OP_FILL], dtype=torch.int32).to(dev)
+        a.kstep, a.tgrid = res["kstep"].data_ptr(), res["grid"].data_ptr()
+        if trajp is not None:  # False: a slot holding a null base; True: a [steps + 1] trajectory of NaN
+            if trajp:
+                res["traj"] = _guarded((steps + 1, B, N, mel), dev)
+            res["trajp"] = torch.tensor([_dp(res["traj"]) if trajp else 0], dtype=torch.int64).to(dev)
+            a.trajp = res["trajp"].data_ptr()
+        if table is not None:
+            table = _f32(table, dev)
+            assert table.shape[0] >= n_count
+            nn = table.shape[1] if next_n is None else int(next_n)
+            res["next_dst"] = _guarded((nn,), dev)
+            a.next_src, a.next_stride, a.next_n, a.next_dst = table.data_ptr(), table.shape[1], nn, _dp(res["next_dst"])
+        if arrive:
+            res["arrive"] = torch.tensor([0, OP_FILL], dtype=torch.int32).to(dev)
+            a.arrive = res["arrive"].data_ptr()
+            if tick is not None:
+                res["tick"] = torch.tensor([int(tick), OP_FILL], dtype=torch.int32).to(dev)
+                a.tick = res["tick"].data_ptr()
+    _glue(name, _lib.stream_handle(dev), ctypes.byref(a))
+    return res
+
+
+def op_cfg_euler(y, p, p_row_off=0, use_cfg=True, cfg=2.0, compute="fp32", ypad=None, dt=None, traj=False, k=None,
+                 tgrid=None, table=None, next_n=None, trajp=True, arrive=True, tick=0):
+    """One cfg_euler launch on a copy of y [B, N, mel] with predictions p [S, rows, p_ld] (sequence B + b is the
+    unconditional branch). ypad: None, or the compute mode whose operand copy [B N, 128] to refresh. Host form: dt,
+    traj (a trajectory slot). Device-indexed form (k given): tgrid (host values, nfe + 1), table [nfe, stride] (its
+    row k + 1 goes to next_dst [next_n]), trajp (None: no slot pointer, False: a null base, True: a [nfe + 1, B, N,
+    mel] trajectory), arrive (the step-index bump), tick (None: no tick word). Returns a dict of every buffer the
+    launch may write: y, ypad, traj, next_dst, kstep, arrive, tick (int words come with one fill word behind)."""
+    n = None if k is None else len(tgrid) - 1
+    return _op_step("f5h_op_cfg_euler", _lib.F5H_EULER, y, p, p_row_off, use_cfg, cfg, compute, ypad, None, dt, traj,
+                    k, tgrid, n, table, next_n, trajp if k is not None else None, arrive, tick)
+
+
+def op_cfg_rk(method, y, p, e, sgrid, kbuf=None, p_row_off=0, use_cfg=True, cfg=2.0, compute="fp32", table=None,
+              next_n=None, trajp=True, arrive=True, tick=0):
+    """One cfg_rk launch (method "midpoint" / "rk4") for evaluation e of the steps of sgrid (host values), on copies
+    of y and kbuf [3, B N mel] (rk4). Returns the dict of op_cfg_euler plus kbuf; kstep is the evaluation counter."""
+    m = _lib.ODE_METHOD[method]
+    stages = {1: 2, 2: 4}[m]
+    return _op_step("f5h_op_cfg_rk", m, y, p, p_row_off, use_cfg, cfg, compute, compute, kbuf, None, False, e, sgrid,
+                    stages * (len(sgrid) - 1), table, next_n, trajp, arrive, tick)
+
+
 def attn_force_safe(on: bool):
     """Test hook: every later 16-bit attention launch reruns its key loop in the lazy-running-max form."""
     _lib.check(_lib.lib().f5h_attn_force_safe(int(bool(on))), "attn_force_safe")

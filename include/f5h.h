@@ -555,6 +555,107 @@ int f5h_op_grn_ragged(void* stream, int32_t compute, int32_t S, int32_t Lmax, in
                       const int32_t* seg_off, const float* x, const float* gamma, const float* beta, float* out,
                       void* workspace, size_t workspace_bytes);
 
+/* Op-level entry points of the audio glue, prologue and ODE step kernels (tests/test_gpu_glue_ops.py). Unlike the
+ * hooks above these stage nothing: every pointer is a device pointer in the type the kernel reads or writes (a buffer
+ * in the operand dtype is bf16 / fp16 memory, "(operand)" below), each hook makes one launcher call on `stream`, and
+ * shapes outside the launcher's contract return F5H_EINVAL before any device work. Tables the kernel reads from
+ * device memory (segment offsets, lengths, counters) cannot be checked here: the caller guarantees them.
+ *
+ * Log-mel front end. mel_frames: wav [B, L] -> frames [B * T, n_fft], T = 1 + L / hop, frame t of wave b =
+ * wav[b][reflect(t hop + j - n_fft/2)] (torch.stft center=True, pad_mode "reflect"); L > n_fft / 2. The ragged form:
+ * wave s is wav[s * wav_stride .. + len[s]), its frames are rows [frame_off[s], frame_off[s+1]) of frames [R, n_fft]
+ * (frame_off [B+1], len [B]: device int32; every len[s] > n_fft / 2, frame_off[s+1] - frame_off[s] = 1 + len[s] / hop).
+ * mel_mag: spec [rows, ld_spec] of interleaved (re, im) -> mag [rows, ld_mag] = |.| for columns < bins, 0 beyond.
+ * mel_log: mel [B * T, n_mels] -> out [B, n_mels, T] = log(max(mel, 1e-5)) (NaN stays NaN). The ragged form: out
+ * [B, T_out, n_mels], row t of wave s = log(max(mel[frame_off[s] + t], 1e-5)) for t < T_s, exact 0 up to T_out. */
+int f5h_op_mel_frames(void* stream, int32_t B, int32_t L, int32_t n_fft, int32_t hop, const float* wav,
+                      float* frames);
+int f5h_op_mel_frames_ragged(void* stream, int32_t B, int32_t R, int32_t n_fft, int32_t hop, const float* wav,
+                             int64_t wav_stride, const int32_t* frame_off, const int32_t* len, float* frames);
+int f5h_op_mel_mag(void* stream, int64_t rows, int32_t bins, int32_t ld_spec, int32_t ld_mag, const float* spec,
+                   float* mag);
+int f5h_op_mel_log(void* stream, int32_t B, int32_t T, int32_t n_mels, const float* mel, float* out);
+int f5h_op_mel_log_ragged(void* stream, int32_t B, int32_t T_out, int32_t n_mels, const float* mel,
+                          const int32_t* frame_off, float* out);
+/* Vocos decoder glue (compute: F5H_FP32 or F5H_BF16). imcol: the embed conv's im2col, mel [B, C, T] -> out
+ * [B * T, Kp] (operand), out[b T + t][7 c + j] = mel[b][c][t + j - 3] (0 outside [0, T)), columns [7 C, Kp) zero;
+ * Kp >= 7 C, Kp % 64 == 0. The ragged form gathers from src[s row_stride + (start[s] + q) frame_stride + c chan_stride]
+ * into packed rows [seg_off[s], seg_off[s+1]) of out [R, Kp], taps outside the utterance's own frames zero (seg_off
+ * [B+1], start [B]: device int32). spec: rows of ld floats in place, columns (2k, 2k+1) = (log-magnitude m, phase p)
+ * of bin k < bins become min(exp(m), 100) (cos p, sin p) (NaN in m or p stays NaN), columns [2 bins, ld) zero.
+ * ola: frames [B * T, n_fft] (already windowed), win [n_fft] -> y [B, (T - 1) hop], torch.istft(center=True)'s
+ * overlap-add over the squared-window envelope; T = 1 launches nothing; n_fft % hop == 0. The ragged form: packed
+ * frames [R, n_fft], utterance s at sample (seg_off[s] - s) hop of y, (len_s - 1) hop samples. */
+int f5h_op_vocos_imcol(void* stream, int32_t compute, int32_t B, int32_t T, int32_t C, int32_t Kp, const float* mel,
+                       void* out);
+int f5h_op_vocos_imcol_ragged(void* stream, int32_t compute, int32_t B, int32_t R, int32_t C, int32_t Kp,
+                              const float* src, int64_t row_stride, int64_t frame_stride, int64_t chan_stride,
+                              const int32_t* seg_off, const int32_t* start, void* out);
+int f5h_op_vocos_spec(void* stream, int64_t rows, int32_t bins, int32_t ld, float* x);
+int f5h_op_vocos_ola(void* stream, int32_t B, int32_t T, int32_t n_fft, int32_t hop, const float* frames,
+                     const float* win, float* y);
+int f5h_op_vocos_ola_ragged(void* stream, int32_t B, int32_t R, int32_t n_fft, int32_t hop, const float* frames,
+                            const float* win, const int32_t* seg_off, float* y);
+/* Sampler prologue. time_sinus: t [n] (a HOST array, or device memory when t_on_device) -> out [n, 256] =
+ * [sin | cos](1000 t exp(-j ln 1e4 / 127)), 1 <= n <= 512. rope_table: out [L, 32, 2] (cos, sin)(n 10000^(-2j/64)).
+ * text_embed (TextEmbedding.forward, both CFG branches): text [B, nt] int64 (-1 = filler), seq_len [B] or NULL, table
+ * [V, td], freqs [rows, td] or NULL (freq_rows > 0: position n reads row min(n, freq_rows - 1)) -> out_c, out_u
+ * [B, N, td], keep [2 B N] bytes or NULL; with seg_off [B+1] (device) N counts packed rows and the outputs are
+ * [N, td], keep [2 N]. build_ct: the input projection's operand [S N, 128 + roundup(td, 64)] (operand) from cond
+ * [B, N, 100], cond_mask [B N] bytes and the text embeddings [B, N, td]; S = B or 2 B. pack_y: y [rows, mel] ->
+ * ypad [rows, 128] (operand), columns >= mel zero. masks, by kind: 0 rowkeep: src = dur [B] int32 -> out [S L] bytes
+ * (pos < off or pos - off < dur[s % B]); 1 kvlen: out [S] int32 = dur[s % B] + off (L unused); 2 textkeep: src = text
+ * [B, L] int64 -> out [S L] bytes (!= -1); 3 textlen: out [S] int32 = 1 + the last position != -1 (0: none). S % B
+ * == 0. final_where_out: out = where(cond_mask, cond, y) over [B, N, mel], all NaN when *fault != 0 (fault NULL:
+ * never). copy_pred: dst [S, L - row_off, mel] = p[(s L + row_off + n) p_ld + c], all NaN when *fault != 0. */
+int f5h_op_time_sinus(void* stream, int32_t t_on_device, int32_t n, const float* t, float* out);
+int f5h_op_rope_table(void* stream, int32_t L, float* out);
+int f5h_op_text_embed(void* stream, int32_t B, int32_t nt, int32_t N, int32_t td, const int64_t* text,
+                      const int32_t* seq_len, const float* table, const float* freqs, int32_t freq_rows,
+                      int32_t mask_padding, float* out_c, float* out_u, uint8_t* keep, const int32_t* seg_off);
+int f5h_op_build_ct(void* stream, int32_t compute, int32_t B, int32_t N, int32_t td, int32_t S, int32_t drop_audio,
+                    int32_t drop_text, const float* cond, const uint8_t* cond_mask, const float* text_c,
+                    const float* text_u, void* out);
+int f5h_op_pack_y(void* stream, int32_t compute, int32_t rows, int32_t mel, const float* y, void* ypad);
+int f5h_op_masks(void* stream, int32_t kind, int32_t B, int32_t S, int32_t L, int32_t off, const void* src,
+                 void* out);
+int f5h_op_final_where_out(void* stream, int32_t B, int32_t N, int32_t mel, const float* cond,
+                           const uint8_t* cond_mask, const float* y, float* out, const uint32_t* fault);
+int f5h_op_copy_pred(void* stream, int32_t S, int32_t L, int32_t row_off, int32_t mel, int64_t p_ld, const float* p,
+                     float* dst, const uint32_t* fault);
+/* CFG + one ODE update launch. v = pc + (pc - pu) cfg (pc alone when !use_cfg) with pc = p[b p_seq_stride +
+ * (p_row_off + n) p_ld + c] and pu the same of sequence B + b. f5h_op_cfg_euler (method 0): y += dt v, the new y also
+ * to ypad [B N, 128] (operand, or NULL) and to the trajectory slot. Host form (kstep NULL): dt and traj (a slot, or
+ * NULL) as given. Device-indexed form: k = *kstep, dt = tgrid[k+1] - tgrid[k], slot (*trajp) + (k + 1) B N mel
+ * (trajp NULL or *trajp NULL: none); next_dst[0, next_n) = next_src[(k + 1) next_stride ..] while k + 1 < nfe; with
+ * arrive (zero before the launch) the last workgroup sets *kstep = k + 1, *arrive = 0 and bumps *tick (or NULL).
+ * f5h_op_cfg_rk (method 1 midpoint, 2 rk4): one evaluation e = *kstep of neval = nfe, step k = e / stages, stage
+ * e % stages; a non-final stage writes the next stage point to ypad only (rk4 keeps its slope in kbuf [3][B N mel]),
+ * the final stage updates y, ypad and trajectory slot k + 1; table row e + 1 and the counter as above. mel <= 128. */
+typedef struct f5h_op_step_args {
+  int32_t compute, method;
+  int32_t B, N, mel, use_cfg;
+  float cfg, dt;
+  float* y;
+  const float* p;
+  int64_t p_seq_stride, p_ld;
+  int32_t p_row_off, nfe;
+  void* ypad;
+  float* traj;
+  float* kbuf;
+  int32_t* kstep;
+  const float* tgrid;
+  float* const* trajp;
+  const float* next_src;
+  int64_t next_stride;
+  int32_t next_n;
+  float* next_dst;
+  uint32_t* arrive;
+  int32_t* tick;
+} f5h_op_step_args;
+int f5h_op_cfg_euler(void* stream, const f5h_op_step_args* args);
+int f5h_op_cfg_rk(void* stream, const f5h_op_step_args* args);
+
 /* Tuning/test hook: pin the 16-bit GEMM tile configuration for all later launches in this
  * process (0, 1, 5, 11, 12, 13), or -1 to restore the automatic per-shape choice. */
 int f5h_gemm_force_config(int32_t cfg);

@@ -6,6 +6,7 @@ already rounded to the compute mode's operand dtype where the kernel reads that 
 from __future__ import annotations
 
 import functools
+import math
 
 import torch
 
@@ -428,3 +429,278 @@ def scale_cols_case(compute, rows, K):
     g = _gen(10, rows, K)
     W = torch.randn(rows, K, generator=g)
     return dict(W=W, W_read=R.rnd(W, compute), g=1.0 + 0.5 * torch.randn(K, generator=g))
+
+
+# ================================================================ audio glue, prologue and ODE step kernels
+# (tests/test_gpu_glue_ops.py, and the same inputs in tests/test_op_refs.py)
+NAN, INF = float("nan"), float("inf")
+
+# ---------------------------------------------------------------- mel_frames
+# (n_fft, hop, L), B = 3 (a read across the batch seam lands in the neighbour's samples). n_fft 64: L 33 is the
+# shortest legal wave (L > n_fft/2), its frames reflect at both ends at once; 48 and 64 are multiples of the hop (the
+# last frame starts exactly at the last sample's window); 1000 has interior frames without reflection. n_fft 1024 /
+# hop 256 (the product's): 513 the shortest, 1300 several blocks.
+MEL_FRAMES_CASES = [(64, 16, 33), (64, 16, 48), (64, 16, 64), (64, 16, 1000), (1024, 256, 513), (1024, 256, 1300)]
+MEL_FRAMES_B = 3
+# one ragged batch: the shortest wave first, the longest next to it, a hop multiple, an odd one; the row stride is
+# longer than the longest wave and everything past a wave's length is NaN (never to be read)
+MEL_RAGGED = dict(n_fft=64, hop=16, lens=(33, 1000, 64, 257), wav_st=1024)
+
+
+@functools.lru_cache(maxsize=None)
+def mel_frames_case(n_fft, hop, L):
+    return torch.randn(MEL_FRAMES_B, L, generator=_gen(20, n_fft, hop, L))
+
+
+@functools.lru_cache(maxsize=None)
+def mel_frames_ragged_case():
+    m = MEL_RAGGED
+    wav = torch.full((len(m["lens"]), m["wav_st"]), NAN)
+    g = _gen(21)
+    for s, n in enumerate(m["lens"]):
+        wav[s, :n] = torch.randn(n, generator=g)
+    return wav
+
+
+# ---------------------------------------------------------------- mel_mag
+# rows 5 x 576 = 2880 outputs: 12 blocks, the last ragged; bins 513 odd; ld_spec 1088 > 2 bins and ld_mag 576 > bins as
+# in the product (K padding of the two GEMMs). Magnitudes from 1e-6 to 1e3 (squares 1e-12 .. 1e6), exact zero pairs,
+# and NaN in the spec columns past 2 bins, which the kernel must not read; the mag pad columns must come back zero.
+MEL_MAG = dict(rows=5, bins=513, ld_spec=1088, ld_mag=576)
+
+
+@functools.lru_cache(maxsize=None)
+def mel_mag_case():
+    m = MEL_MAG
+    g = _gen(22)
+    mag = 10.0 ** (torch.rand(m["rows"], m["bins"], 2, generator=g) * 9.0 - 6.0)
+    z = mag * torch.where(torch.rand(m["rows"], m["bins"], 2, generator=g) < 0.5, -1.0, 1.0)
+    z[:, ::37] = 0.0       # exact zeros: |0| = 0, not NaN
+    z[0, 1, 0] = 0.0       # one component zero
+    spec = torch.full((m["rows"], m["ld_spec"]), NAN)
+    spec[:, :2 * m["bins"]] = z.reshape(m["rows"], -1)
+    return dict(spec=spec, u_out=0.0, **m)
+
+
+def mel_mag_ref(c, dtype, variant=None):
+    return R.mel_mag(c["spec"], c["bins"], c["ld_mag"], dtype=dtype, variant=variant)
+
+
+# ---------------------------------------------------------------- mel_log
+# B = 2, n_mels = 100, T = 1 (the transposition degenerates) and 3; the ragged form with T_s = (1, 3) in T_out = 4.
+# Values from 1e-7 to 1e2 around the clamp, and in fixed places 0, 1e-5 and its two float32 neighbours (the clamp's
+# edge: below it log(1e-5), above it the value's own log), 1 (log = 0 exactly), +inf (stays +inf) and NaN (stays NaN).
+MEL_LOG_T = (1, 3)
+MEL_LOG_RAGGED = dict(frames=(1, 3), T_out=4)
+MEL_LOG_B, MEL_LOG_NMELS = 2, 100
+
+
+@functools.lru_cache(maxsize=None)
+def mel_log_case(rows):
+    g = _gen(23, rows)
+    mel = 10.0 ** (torch.rand(rows, MEL_LOG_NMELS, generator=g) * 9.0 - 7.0)
+    e = torch.tensor(1e-5, dtype=torch.float32)
+    below, above = torch.nextafter(e, torch.tensor(0.0)), torch.nextafter(e, torch.tensor(1.0))
+    for r in range(rows):  # every row (every frame of every wave) holds the specials, at row-dependent bins
+        mel[r, torch.arange(7) * 13 + r] = torch.stack((torch.tensor(0.0), e, below, above, torch.tensor(1.0),
+                                                         torch.tensor(INF), torch.tensor(NAN)))
+    return dict(mel=mel, u_out=0.0)
+
+
+def mel_log_ref(c, frames, T_out, dtype, variant=None):
+    return R.mel_log(c["mel"], frames, T_out, dtype=dtype, variant=variant)
+
+
+# ---------------------------------------------------------------- vocos_im2col
+# C = 100 mel bins -> 700 columns, Kp = 704 (the GEMM's K padding: columns 700..703 zero). T 1, 2, 3 are shorter than
+# the window's half (every tap but the centre ones is padding), 4 and 7 around the window, 8 longer; B = 2: a tap
+# across the batch seam would read the neighbour's frames. Ragged: lengths (1, 2, 9, 4) from [B][N][C] (start > 0) and
+# from [B][C][T], with NaN in every source frame outside [start, start + len).
+IM2COL = dict(C=100, Kp=704, B=2, Ts=(1, 2, 3, 4, 7, 8))
+IM2COL_RAGGED = dict(lens=(1, 2, 9, 4), starts=(3, 1, 2, 5), frames=12)
+
+
+@functools.lru_cache(maxsize=None)
+def im2col_case(T):
+    return torch.randn(IM2COL["B"], IM2COL["C"], T, generator=_gen(24, T))
+
+
+@functools.lru_cache(maxsize=None)
+def im2col_ragged_case(layout):
+    """(src in `layout` with NaN outside every utterance's frames, [utterance mel [1, C, len]])."""
+    m, C = IM2COL_RAGGED, IM2COL["C"]
+    g = _gen(25)
+    src = torch.full((len(m["lens"]), m["frames"], C), NAN)  # [B][N][C]
+    utts = []
+    for s, (st, n) in enumerate(zip(m["starts"], m["lens"])):
+        x = torch.randn(n, C, generator=g)
+        src[s, st:st + n] = x
+        utts.append(x.t()[None].contiguous())
+    return (src if layout == "BNC" else src.transpose(1, 2).contiguous()), utts
+
+
+# ---------------------------------------------------------------- vocos_spec
+# rows 3 x 544 pairs = 1632 threads (7 blocks, ragged), bins 513 of ld 1088 as in the product. m spans [-20, 10] across
+# the clip at log(100) = 4.605 (values on both sides within 1e-3 of it too), m = +inf (magnitude 100) and -inf (0);
+# phases near 0 and +-pi (the sign changes of sin / cos) and near 1e2 and 1e4 (argument reduction). NaN in m alone and
+# in p alone must both give a NaN pair; the pad pairs start as NaN and must come back zero.
+SPEC = dict(rows=3, bins=513, ld=1088)
+
+
+@functools.lru_cache(maxsize=None)
+def spec_case():
+    m = SPEC
+    g = _gen(26)
+    rows, bins = m["rows"], m["bins"]
+    mm = torch.rand(rows, bins, generator=g) * 30.0 - 20.0
+    mm[:, 10:20] = math.log(100.0) + torch.linspace(-1e-3, 1e-3, 10)
+    centre = torch.tensor([0.0, math.pi, -math.pi, 1e2, 1e4])[torch.randint(0, 5, (rows, bins), generator=g)]
+    pp = centre + 0.01 * torch.randn(rows, bins, generator=g)
+    pp[:, 30:35] = torch.tensor([0.0, math.pi, -math.pi, 1e2, 1e4])
+    mm[0, 40], mm[1, 41] = INF, -INF
+    mm[0, 5] = NAN   # NaN log-magnitude, finite phase
+    pp[1, 7] = NAN   # finite log-magnitude, NaN phase
+    x = torch.full((rows, m["ld"]), NAN)
+    x[:, :2 * bins] = torch.stack((mm, pp), dim=-1).reshape(rows, -1)
+    return dict(x=x, u_out=0.0, **m)
+
+
+def spec_ref(c, dtype, variant=None):
+    return R.vocos_spec(c["x"], c["bins"], dtype=dtype, variant=variant)
+
+
+# ---------------------------------------------------------------- vocos_ola
+# (n_fft, hop): the product's 1024 / 256 and the small 64 / 16, four frames per window both. B = 2. T = 1 has no
+# samples (no launch); 2, 3: fewer frames than a window covers; 4: as many; 5, 9: more (interior samples under four
+# frames). Ragged: lengths (1, 2, 5, 1, 9) -- one-frame utterances at the start and in the middle contribute nothing
+# and shift nobody -- and a batch of one-frame utterances only (no launch).
+OLA_FFT = ((1024, 256), (64, 16))
+OLA_B = 2
+OLA_TS = (2, 3, 4, 5, 9)
+OLA_RAGGED_LENS = (1, 2, 5, 1, 9)
+
+
+@functools.lru_cache(maxsize=None)
+def ola_case(n_fft, hop, lens):
+    """Packed windowed frames [sum lens, n_fft] and the periodic Hann window."""
+    win = torch.hann_window(n_fft, periodic=True)
+    fr = torch.randn(sum(lens), n_fft, generator=_gen(27, n_fft, hop, *lens)) * win
+    return dict(frames=fr, win=win, lens=lens, hop=hop, u_out=0.0)
+
+
+def ola_ref(c, dtype, variant=None):
+    return R.vocos_ola(c["frames"], c["win"], c["lens"], c["hop"], dtype=dtype, variant=variant)
+
+
+# ---------------------------------------------------------------- time_sinus
+# n = 1, 5 (one block, ragged) and 512 (the launcher's limit, 256 blocks). t = 0 (sin 0, cos 1 exactly), 1e-5 (the
+# sway grid's first steps), 0.03125, 0.5 and 1 (arguments up to 1000 rad).
+TIME_SINUS_T = {1: (0.03125,), 5: (0.0, 1e-5, 0.03125, 0.5, 1.0), 512: tuple(torch.linspace(0, 1, 512).tolist())}
+
+
+def time_sinus_case(n):
+    return dict(t=torch.tensor(TIME_SINUS_T[n], dtype=torch.float32), u_out=0.0)
+
+
+def time_sinus_ref(c, dtype, variant=None):
+    return R.time_sinus(c["t"], dtype=dtype, variant=variant)
+
+
+ROPE_LS = (1, 70, 8192)  # one row; a ragged last block; the engine's longest sequence
+
+
+# ---------------------------------------------------------------- text_embed
+# B = 2, nt = 5. Row 0 has a filler in the interior, row 1 fillers at the end. N = 3 cuts the text, 5 = nt, 9 pads it.
+# td = 100 leaves a ragged last 64-lane group, 512 fills eight. seq_len None, or per sample (N, N - 2): sample 1's last
+# positions are dropped. freqs: None, the full table, or a 4-row table with N = 9 (positions 4..8 read row 3).
+TEXT = torch.tensor([[3, -1, 7, 2, 9], [4, 5, 6, -1, -1]])
+TEXT_V = 12
+TEXT_CASES = [(N, td, per, fr, mp) for N in (3, 5, 9) for td in (100, 512) for per in (False, True)
+              for fr in ((None, "full", "rows4") if N == 9 else (None, "full")) for mp in (False, True)]
+TEXT_SEG_LENS = (7, 3)  # the ragged form: utterance lengths (one pads its text, one cuts it)
+
+
+@functools.lru_cache(maxsize=None)
+def text_table(td):
+    from oracle import ref_cpu
+
+    return torch.randn(TEXT_V, td, generator=_gen(28, td)), ref_cpu.freqs_cis_table(td, 16)
+
+
+def text_embed_args(N, td, per, fr, mp):
+    table, freqs = text_table(td)
+    return dict(table=table, N=N, seq_len=(N, max(1, N - 2)) if per else None,
+                freqs=None if fr is None else (freqs if fr == "full" else freqs[:4].contiguous()),
+                freq_rows=4 if fr == "rows4" else 0, mask_padding=mp)
+
+
+# ---------------------------------------------------------------- build_ct, pack_y, masks, final_where_out, copy_pred
+# build_ct: (S, drop_audio, drop_text) with B = 2: both branches (S = 4) and the single-branch forward (S = 2) under
+# the four drop-flag combinations; N = 5; td 100 (text columns 100..127 of the text block are zero padding) and 64 (no
+# padding); a cond_mask with kept and dropped frames in both samples.
+CT_CASES = [(4, 0, 0), (2, 0, 0), (2, 1, 0), (2, 0, 1), (2, 1, 1)]
+CT_TDS = (100, 64)
+
+
+@functools.lru_cache(maxsize=None)
+def ct_case(td):
+    g = _gen(29, td)
+    B, N = 2, 5
+    return dict(cond=torch.randn(B, N, 100, generator=g), cond_mask=torch.tensor([[1, 1, 0, 0, 1], [0, 1, 1, 0, 0]]),
+                text_c=torch.randn(B, N, td, generator=g), text_u=torch.randn(B, N, td, generator=g))
+
+
+PACK_Y = dict(rows=7, mels=(100, 80))  # 896 outputs: 3.5 blocks; mel 100 and 80 leave 28 / 48 zero pad columns
+# masks: B = 3, S = 2 B (the unconditional sequences reuse sample s % B); durations below, at and above L; off 0, 1
+# (the UNetT time token's row). build_textlen: nt 1, 64 (one pass of the wave), 65 (one lane wraps), 130 (three
+# passes); rows: all filler (0), a filler in the interior (fillers do not end the text), the last position valid (nt).
+MASK_DUR, MASK_L = (2, 6, 9), 6
+TEXTLEN_NTS = (1, 64, 65, 130)
+
+
+def textlen_case(nt):
+    text = torch.arange(3 * nt).reshape(3, nt) % 11
+    text[0] = -1
+    text[1, nt // 2:] = -1
+    text[1, : nt // 4] = -1  # (interior / leading fillers before the last valid position)
+    text[2, : nt - 1] = -1   # only the last position valid
+    return text
+
+
+@functools.lru_cache(maxsize=None)
+def where_case():
+    g = _gen(30)
+    B, N, mel = 2, 5, 100
+    return dict(cond=torch.randn(B, N, mel, generator=g), y=torch.randn(B, N, mel, generator=g),
+                cond_mask=torch.tensor([[1, 1, 0, 0, 1], [0, 0, 1, 0, 0]]))
+
+
+@functools.lru_cache(maxsize=None)
+def copy_pred_case():
+    """p [S = 2, L = 6, p_ld = 128] with NaN in the pad columns mel..127 (never copied)."""
+    p = torch.randn(2, 6, 128, generator=_gen(31))
+    p[..., 100:] = NAN
+    return p
+
+
+# ---------------------------------------------------------------- cfg_euler / cfg_rk
+# (B, N, mel): 2 x 1 x 100 = 200 elements, one block; 2 x 166 x 99 = 128 * 256 + 100: the launch is capped at 128
+# blocks, so the grid-stride loop wraps for the last 100. p_row_off 1 with p_ld 128 is UNetT's prediction (row 0 the
+# time token, pad columns NaN here), p_row_off 0 with p_ld = mel the DiT's.
+STEP_SHAPES = ((2, 1, 100), (2, 166, 99))
+STEP_P_LAYOUTS = ((1, 128), (0, None))
+STEP_GRID = (0.0, 0.0625, 0.21875, 0.5, 1.0)  # nfe 4, unequal steps
+STEP_CFG = 2.3
+
+
+@functools.lru_cache(maxsize=None)
+def step_case(B, N, mel, row_off, p_ld, seed=0):
+    g = _gen(32, B, N, mel, row_off, seed)
+    p = torch.full((2 * B, N + row_off, p_ld or mel), NAN)
+    p[:, row_off:, :mel] = torch.randn(2 * B, N, mel, generator=g)
+    return dict(y=torch.randn(B, N, mel, generator=g), p=p)
+
+
+def step_table(n, stride=24):
+    """A table of n rows (the AdaLN / time-token rows of the step bookkeeping), row i = i + column / 100."""
+    return torch.arange(n)[:, None].float() + torch.arange(stride)[None, :].float() / 100.0

@@ -342,3 +342,246 @@ def scale_cols(W_read, g, compute, variant=None):
     if variant == "g_by_row":
         return rnd(W_read.float() * gf[torch.arange(W_read.shape[0]) % gf.numel()][:, None], compute)
     return rnd(W_read.float() * gf[None, :], compute)
+
+
+# ================================================================ audio glue, prologue and ODE step kernels
+# (tests/test_gpu_glue_ops.py). Two kinds of reference. The gathers and the uncontracted fp32 step arithmetic have a
+# float32 torch restatement the kernel must equal bit for bit; tests/test_op_refs.py ties each restatement to an
+# independent definition (F.conv1d, torch.stft, the oracle's TextEmbedding, tests/ode_reference.py). The kernels with
+# transcendental functions or sums have R64 / R32 forms and WRONG_* variants as above.
+def assert_close_special(out, r64, r32, u_out, what):
+    """assert_close for references with NaN or +-inf elements: there `out` must hold the same special value; the
+    tolerance is asserted over the finite elements (the special ones count as exact zeros on every side)."""
+    out, r64, r32 = out.double(), r64.double(), r32.double()
+    assert torch.equal(torch.isnan(out), torch.isnan(r64)), f"{what}: NaN where the reference has none, or lost"
+    inf = torch.isinf(r64)
+    assert torch.equal(out[inf], r64[inf]), f"{what}: +-inf of the reference not reproduced"
+    sp = ~torch.isfinite(r64)
+    z = lambda t: torch.where(sp, torch.zeros((), dtype=t.dtype), t)  # noqa: E731
+    return assert_close(z(out), z(r64), z(r32), u_out, what)
+
+
+def same_specials(a, b):
+    """NaN and +-inf in the same places with the same signs."""
+    sa, sb = ~torch.isfinite(a), ~torch.isfinite(b)
+    return torch.equal(sa, sb) and torch.equal(torch.isnan(a), torch.isnan(b)) and \
+        torch.equal(a[sa & ~torch.isnan(a)].double(), b[sb & ~torch.isnan(b)].double())
+
+
+# ---------------------------------------------------------------- bitwise restatements: gathers
+def mel_frames(wav, n_fft, hop):
+    """torch.stft(center=True, pad_mode="reflect")'s framing: wav [B, L] -> [B, 1 + L // hop, n_fft]."""
+    padded = F.pad(wav[:, None, :], (n_fft // 2, n_fft // 2), mode="reflect")[:, 0]
+    return padded.unfold(-1, n_fft, hop).contiguous()
+
+
+def im2col7(mel, Kp, compute="fp32"):
+    """Conv1d(k 7, pad 3)'s im2col: mel [B, C, T] -> [B * T, Kp], column 7 c + j = mel[b, c, t + j - 3], zero taps
+    outside [0, T) and zero columns from 7 C on; rounded to the operand dtype."""
+    B, C, T = mel.shape
+    cols = F.pad(mel, (3, 3)).unfold(-1, 7, 1).permute(0, 2, 1, 3).reshape(B * T, C * 7)
+    return F.pad(cols, (0, Kp - C * 7)).to(OP_DTYPE[compute])
+
+
+def text_embed(text, table, N, seq_len=None, freqs=None, freq_rows=0, mask_padding=False):
+    """TextEmbedding.forward for both CFG branches (dit.py:86-120; mmdit.py:42-63 for the position clamp): tokens + 1
+    (filler 0), cut or padded to N, positions past the sample's seq_len dropped, the filler mask taken before
+    drop_text, Embedding, + freqs_cis, masked_fill of filler rows (only with the extra modelling, i.e. with freqs).
+    Returns (cond [B,N,td], uncond [B,N,td], keep [2,B,N] uint8: 0 where a filler row was zeroed)."""
+    B = text.shape[0]
+    tok = F.pad(text[:, :N] + 1, (0, max(0, N - text.shape[1])), value=0)
+    valid = torch.ones(B, N, dtype=torch.bool) if seq_len is None else \
+        torch.arange(N)[None, :] < torch.as_tensor(seq_len)[:, None]
+    tok = tok.masked_fill(~valid, 0)
+    fill = tok == 0
+    zero = torch.zeros((), dtype=table.dtype)
+    ec = torch.where(valid[..., None], table[tok], zero)
+    eu = torch.where(valid[..., None], table[torch.zeros_like(tok)], zero)
+    zero_row = torch.zeros(B, N, dtype=torch.bool)
+    if freqs is not None:
+        pos = torch.arange(N)
+        if freq_rows:
+            pos = pos.clamp(max=freq_rows - 1)
+        f = torch.where(valid[..., None], freqs[pos][None], zero)
+        ec, eu = ec + f, eu + f
+        if mask_padding:
+            zero_row = fill
+            ec, eu = ec.masked_fill(fill[..., None], 0.0), eu.masked_fill(fill[..., None], 0.0)
+    keep = (~zero_row).to(torch.uint8)
+    return ec, eu, torch.stack((keep, keep))
+
+
+def build_ct(cond, cond_mask, text_c, text_u, S, drop_audio=False, drop_text=False, compute="fp32"):
+    """InputEmbedding's operand (dit.py:155-156, 347-350): per sequence s and frame [step_cond | 0 .. 128 | text |
+    0 .. roundup(td, 64)]; step_cond = where(cond_mask, cond, 0) for the conditional sequences s < B unless
+    drop_audio, zeros for the unconditional ones; text = the dropped-text embedding for s >= B or with drop_text."""
+    B, N, mel = cond.shape
+    td = text_c.shape[-1]
+    out = torch.zeros(S, N, 128 + (td + 63) // 64 * 64)
+    for s in range(S):
+        b = s % B
+        if s < B and not drop_audio:
+            out[s, :, :mel] = torch.where(cond_mask[b].bool()[:, None], cond[b], torch.zeros(()))
+        out[s, :, 128:128 + td] = (text_c if (s < B and not drop_text) else text_u)[b]
+    return out.reshape(S * N, -1).to(OP_DTYPE[compute])
+
+
+def pack_y(y, compute="fp32"):
+    return F.pad(y, (0, 128 - y.shape[-1])).to(OP_DTYPE[compute])
+
+
+def masks(kind, src, S, L=0, off=0):
+    """build_rowkeep / build_kvlen from dur [B]; build_textkeep / build_textlen from text [B, nt] (-1 = filler)."""
+    B = src.shape[0]
+    idx = torch.arange(S) % B
+    if kind == "build_rowkeep":
+        pos = torch.arange(L)[None, :]
+        return ((pos < off) | (pos - off < src[idx].long()[:, None])).to(torch.uint8)
+    if kind == "build_kvlen":
+        return (src[idx] + off).to(torch.int32)
+    real = src[idx] != -1
+    if kind == "build_textkeep":
+        return real.to(torch.uint8)
+    assert kind == "build_textlen"
+    last = (real * (torch.arange(src.shape[1]) + 1)[None, :]).amax(-1)
+    return last.to(torch.int32)
+
+
+def final_where_out(cond, cond_mask, y, fault=None):
+    """cfm.py:223: where(cond_mask, cond, y); NaN everywhere once the give-up word is set."""
+    out = torch.where(cond_mask.bool()[..., None], cond, y)
+    return torch.full_like(out, float("nan")) if fault else out
+
+
+def copy_pred(p, row_off, mel, fault=None):
+    out = p[:, row_off:, :mel].contiguous()
+    return torch.full_like(out, float("nan")) if fault else out
+
+
+# ---------------------------------------------------------------- bitwise restatements: CFG + ODE updates
+def _f32s(v):
+    return torch.tensor(float(v), dtype=torch.float32)
+
+
+def cfg_slope(p, B, N, mel, row_off, use_cfg, cfg):
+    """fn(t, x) = pred + (pred - null_pred) * cfg (cfm.py:190-191), fp32, one rounding per operation."""
+    pc = p[:B, row_off:row_off + N, :mel]
+    if not use_cfg:
+        return pc.clone()
+    return pc + (pc - p[B:2 * B, row_off:row_off + N, :mel]) * _f32s(cfg)
+
+
+def grid_dt(grid, k):
+    g = torch.tensor([float(v) for v in grid], dtype=torch.float32)
+    return g[k + 1] - g[k]
+
+
+def euler_update(y, v, dt):
+    """torchdiffeq euler: y1 = y0 + dt * f."""
+    return y + (_f32s(dt) if not torch.is_tensor(dt) else dt) * v
+
+
+def rk_stage(method, s, y, v, dt, kbuf=None):
+    """One evaluation of torchdiffeq's fixed-grid midpoint / rk4 (3/8 rule) in its written operation order. Returns
+    (the next evaluation's input yn, the slopes kept so far): the final stage's yn is y1."""
+    if method == "midpoint":
+        return (y + v * (_f32s(0.5) * dt) if s == 0 else y + dt * v), kbuf
+    c = _f32s(1.0 / 3.0)
+    K = None if kbuf is None else kbuf.clone()
+    if s == 0:
+        yn = y + (dt * v) * c
+    elif s == 1:
+        yn = y + dt * (v - K[0] * c)
+    elif s == 2:
+        yn = y + dt * ((K[0] - K[1]) + v)
+    else:
+        yn = y + (((K[0] + _f32s(3.0) * (K[1] + K[2])) + v) * dt) * _f32s(0.125)
+    if s < 3:
+        K[s] = v
+    return yn, K
+
+
+def ypad_of(yn, compute):
+    """The refreshed operand copy [B N, mel] (round to nearest even); the pad columns are not the update's."""
+    return yn.reshape(-1, yn.shape[-1]).to(OP_DTYPE[compute])
+
+
+# ---------------------------------------------------------------- R64 / R32 references
+WRONG_MEL_MAG = ("power2",)
+WRONG_MEL_LOG = ("clamp_1e-10", "log10")
+WRONG_SPEC = ("no_clip", "sin_cos_swapped")
+WRONG_OLA = ("window_not_squared", "first_frame_off_by_one", "no_trim")
+WRONG_TIME_SINUS = ("cos_before_sin", "divisor_128", "scale_1")
+
+
+def mel_mag(spec, bins, ld_mag, dtype=torch.float64, variant=None):
+    """torchaudio Spectrogram(power=1): |X_k| of interleaved (re, im) rows; columns [bins, ld_mag) zero."""
+    z = spec[:, :2 * bins].to(dtype).reshape(spec.shape[0], bins, 2)
+    m = z[..., 0] * z[..., 0] + z[..., 1] * z[..., 1]
+    if variant != "power2":
+        m = torch.sqrt(m)
+    return F.pad(m, (0, ld_mag - bins))
+
+
+def mel_log(mel, frames, T_out=None, dtype=torch.float64, variant=None):
+    """get_vocos_mel_spectrogram's tail (modules.py:107-108): mel.clamp(min=1e-5).log(). mel [sum frames, n_mels].
+    T_out None: equal frame counts, returned channel-first [B, n_mels, T] as the reference returns it; else the
+    frame-major zero-padded batch [B, T_out, n_mels] CFM.sample takes."""
+    x = mel.to(dtype).clamp(min=1e-10 if variant == "clamp_1e-10" else 1e-5)
+    x = torch.log10(x) if variant == "log10" else torch.log(x)
+    if T_out is None:
+        return x.reshape(len(frames), frames[0], -1).transpose(1, 2).contiguous()
+    out = torch.zeros(len(frames), T_out, x.shape[-1], dtype=dtype)
+    o = 0
+    for s, t in enumerate(frames):
+        out[s, :t] = x[o:o + t]
+        o += t
+    return out
+
+
+def vocos_spec(x, bins, dtype=torch.float64, variant=None):
+    """ISTFTHead.forward's pointwise part (vocos heads.py): mag = clip(exp(m), max=1e2), S = mag (cos p + i sin p),
+    on columns (2k, 2k+1) = (m, p) of bin k; columns from 2 bins on zero."""
+    z = x[:, :2 * bins].to(dtype).reshape(x.shape[0], bins, 2)
+    mag = torch.exp(z[..., 0])
+    if variant != "no_clip":
+        mag = torch.clip(mag, max=1e2)
+    c, s = torch.cos(z[..., 1]), torch.sin(z[..., 1])
+    if variant == "sin_cos_swapped":
+        c, s = s, c
+    out = torch.stack((mag * c, mag * s), dim=-1).reshape(x.shape[0], 2 * bins)
+    return F.pad(out, (0, x.shape[1] - 2 * bins))
+
+
+def vocos_ola(frames, win, lens, hop, dtype=torch.float64, variant=None):
+    """torch.istft(center=True)'s tail per utterance: overlap-add of the windowed frames over the overlap-added
+    squared window, trimmed by n_fft / 2 at the front, (T - 1) hop samples. frames [sum lens, n_fft] packed; returns
+    the utterances' samples back to back."""
+    n_fft = frames.shape[1]
+    fr, w = frames.to(dtype), win.to(dtype)
+    wenv = w if variant == "window_not_squared" else w * w
+    out, o = [], 0
+    for T in lens:
+        n = (T - 1) * hop + n_fft
+        full, env = torch.zeros(n, dtype=dtype), torch.zeros(n, dtype=dtype)
+        pos = torch.arange(n)
+        first = torch.clamp((pos - n_fft + 1 + hop - 1).div(hop, rounding_mode="floor"), min=0)  # first covering frame
+        for t in range(T):
+            sl = slice(t * hop, t * hop + n_fft)
+            use = torch.ones(n_fft, dtype=torch.bool) if variant != "first_frame_off_by_one" else first[sl] != t
+            full[sl] += torch.where(use, fr[o + t], torch.zeros((), dtype=dtype))
+            env[sl] += torch.where(use, wenv, torch.zeros((), dtype=dtype))
+        lo = 0 if variant == "no_trim" else n_fft // 2
+        out.append((full / env)[lo:lo + (T - 1) * hop])
+        o += T
+    return torch.cat(out)
+
+
+def time_sinus(t, dtype=torch.float64, variant=None):
+    """SinusPositionEmbedding(256) with scale 1000 (modules.py:157-169): emb = log(1e4) / (half - 1), x = scale t
+    exp(-j emb), [sin x | cos x]."""
+    half = 128
+    k = math.log(10000) / (half if variant == "divisor_128" else half - 1)
+    freq = torch.exp(torch.arange(half).to(dtype) * -k)
+    e = (1.0 if variant == "scale_1" else 1000.0) * torch.as_tensor(t).to(dtype)[:, None] * freq[None, :]
+    return torch.cat((e.cos(), e.sin()) if variant == "cos_before_sin" else (e.sin(), e.cos()), dim=-1)

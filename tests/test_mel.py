@@ -61,6 +61,25 @@ def test_mel_hip_matches_oracle(B, L):
 
 
 @pytest.mark.gpu
+def test_mel_hip_nan_sample_gives_nan_frames():
+    """A corrupt sample must not come out as silence: a wave with one NaN sample gives NaN in every bin of exactly
+    the frames whose window covers it (the reference's clamp(min=1e-5).log() keeps NaN), finite values elsewhere."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from f5_tts_amd.mel import MelSpec
+
+    wav = _wav(2, 6000, seed=9)
+    at = 3000  # far from both ends: no frame sees it through the reflection
+    wav[0, at] = float("nan")
+    out = MelSpec()(wav.to(DEV)).cpu()
+    # frame t covers samples [256 t - 512, 256 t + 512)
+    hit = torch.tensor([256 * t - 512 <= at < 256 * t + 512 for t in range(out.shape[-1])])
+    assert int(hit.sum()) == 4
+    assert torch.isnan(out[0][:, hit]).all()
+    assert torch.isfinite(out[0][:, ~hit]).all() and torch.isfinite(out[1]).all()
+
+
+@pytest.mark.gpu
 def test_cfm_sample_raw_wave_cond_and_vocoder_run_on_hip():
     """CFM.sample on raw audio (cfm.py:106-109) goes through the HIP MelSpec: identical to sampling
     from the mel it produces; `vocoder=` (cfm.py:226-227) accepts the HIP Vocos."""

@@ -89,6 +89,23 @@ def test_vocos_fp32_matches_oracle(B, T):
 
 
 @pytest.mark.gpu
+def test_vocos_nan_frame_gives_nan_samples():
+    """A corrupt mel frame must not come out as plausible audio: the samples under the NaN frame's window are NaN
+    (torch.clip(exp, max=1e2) keeps NaN). The convolutions (embed and 8 depthwise, k 7) carry it 27 frames each way
+    and the overlap-add two more hops; samples further off, and the other utterance, are finite."""
+    _gpu()
+    v, _ = _vocos("fp32")
+    mel = _mel(2, 100, seed=13)
+    t0 = 50
+    mel[0, :, t0] = float("nan")
+    out = v.decode(mel.to(DEV)).cpu()
+    assert out.shape == (2, 99 * 256)
+    assert torch.isnan(out[0, 256 * t0 - 512:256 * t0 + 512]).all()  # frame t0 covers samples [256 t0 - 512, + 1024)
+    lo, hi = 256 * (t0 - 27) - 512, 256 * (t0 + 27) + 512
+    assert torch.isfinite(out[0, :lo]).all() and torch.isfinite(out[0, hi:]).all() and torch.isfinite(out[1]).all()
+
+
+@pytest.mark.gpu
 def test_vocos_bf16_close_to_oracle():
     _gpu()
     v, W = _vocos("bf16")
