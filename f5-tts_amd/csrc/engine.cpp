@@ -111,6 +111,11 @@ static void layout(const f5h_engine* e, WS& ws, Bufs& b, int B, int N, int nfe, 
   b.rg_off = rgB ? ws.take<int32_t>((size_t)2 * rgB + 1) : nullptr;
   b.rg_len = rgB ? ws.take<int32_t>((size_t)2 * rgB) : nullptr;
   b.rg_tab = rgB ? ws.take<int2>((size_t)2 * N) : nullptr;
+  // F5H_MXFP8 only, and last, so that every other buffer sits where the bf16 mode has it: the MX8 launches' activation
+  // operand (elements, then scales), a row of max K = max(dim, ff_dim) bytes per stream row (heads * 64 == dim)
+  const size_t kmax = (size_t)std::max(d, a.ff_dim);
+  b.a8 = e->mx8 ? ws.take<uint8_t>(rows * kmax) : nullptr;
+  b.a8s = e->mx8 ? ws.take<uint8_t>(rows * (kmax / 32)) : nullptr;
 }
 
 // ---------------------------------------------------------------- probe
@@ -348,7 +353,15 @@ static int backbone_part(Ctx& c, int s0, int ns, hipStream_t st) {
     const char* v = getenv("F5H_RES32");
     return v && *v == '1';
   }();
-  const bool r16 = bf != 0 && (!dit || !res32);
+  // F5H_MXFP8 (c.mx8: the classes on MX8 operands; 0 runs the bf16 mode's launches exactly): the activation operand
+  // of this part's MX8 launches, and the launch arguments' second half. With any class on, the residual stream is
+  // 16-bit whatever F5H_RES32 says, and the fold, the chain (call_begin) and the out-projection's live_len skip are off.
+  const int mx = dit ? c.mx8 : 0;
+  const size_t mx_kmax = (size_t)std::max(d, a.ff_dim);
+  uint8_t* const a8 = mx ? b.a8 + ro * mx_kmax : nullptr;
+  uint8_t* const a8s = mx ? b.a8s + ro * (mx_kmax / 32) : nullptr;
+  auto mx_ops = [&](const Lin& W) { return Mx8Ops{a8, a8s, W.w8, W.ws, e->mx8_count}; };
+  const bool r16 = bf != 0 && (!dit || !res32 || mx != 0);
   // F5H_DIAG_SKIP_LN=1: timing-only diagnostic, the 16-bit DiT path skips its LayerNorm launches
   // (wrong results; bounds what removing those launches can save). Never set in tests or benches.
   static const bool skip_ln = [] {
@@ -525,8 +538,12 @@ static int backbone_part(Ctx& c, int s0, int ns, hipStream_t st) {
         KCK(rms_norm_g(bf, h, r16, rows, d, Ly.g_attn, aop, st));
       }
     } else {
-      if (do_ln && !qkv_done && !(fold_on && l > 0))
-        KCK(ln_modulate(bf, h, r16, rows, d, ad /*shift_msa*/, ad + d /*scale_msa*/, aop, st));
+      if (do_ln && !qkv_done && !(fold_on && l > 0)) {
+        if (mx & kStoreBit(KC_QKV))
+          KCK(ln_modulate_mx8(h, r16, rows, d, ad /*shift_msa*/, ad + d /*scale_msa*/, a8, a8s, st));
+        else
+          KCK(ln_modulate(bf, h, r16, rows, d, ad /*shift_msa*/, ad + d /*scale_msa*/, aop, st));
+      }
     }
     if (!qkv_done) {
       GemmArgs g = qkv_args(Ly);
@@ -536,9 +553,15 @@ static int backbone_part(Ctx& c, int s0, int ns, hipStream_t st) {
         g.W = Ly.qkv_g.w;
         rms_consumer(g);
       }
-      gemm_policy(c, g, EPI_QKV, KC_QKV);
-      ProbeScope ps(e, KC_QKV, st, &c.site, &g.probe);
-      KCK(gemm(bf, EPI_QKV, g, st));
+      if (mx & kStoreBit(KC_QKV)) {
+        count_store(e, 0);  // (the MX8 kernel has plain stores only)
+        ProbeScope ps(e, KC_QKV, st, &c.site, &g.probe);
+        KCK(gemm_mx8(EPI_QKV, g, mx_ops(Ly.qkv), st));
+      } else {
+        gemm_policy(c, g, EPI_QKV, KC_QKV);
+        ProbeScope ps(e, KC_QKV, st, &c.site, &g.probe);
+        KCK(gemm(bf, EPI_QKV, g, st));
+      }
     }
     qkv_done = false;
     {
@@ -602,20 +625,32 @@ static int backbone_part(Ctx& c, int s0, int ns, hipStream_t st) {
       g.rowkeep = keep;                    // masked_fill of pad rows (modules.py:552-554)
       // row tiles of padding only: no work at all. Only in place (h_in null): a UNetT first-half layer
       // writes x_in + attn into the next buffer, so its pad rows must still be copied there
-      if (keep && !h_in && e->pad_skip && !rms_on) {
+      if (keep && !h_in && e->pad_skip && !rms_on && !mx) {
         g.live_len = b.kvlen + s0;
         g.live_seq = c.L;
       }
       if (fold_on) fold_producer(g, ad + 4 * d /*scale_mlp: hs = h (1 + scale_mlp) for FFN1*/);
       if (rms_on) rms_producer(g);  // the FFN-norm's statistics of h
-      gemm_policy(c, g, epi_resid, KC_OUT);
-      ProbeScope ps(e, KC_OUT, st, &c.site, &g.probe);
-      KCK(gemm(bf, epi_resid, g, st));
+      if (mx & kStoreBit(KC_OUT)) {
+        // (rows of o the attention's pad-row skip left unwritten quantise to whatever they hold: they feed pad rows
+        // of the product only, which keep their residual)
+        KCK(quant_rows_mx8(o, rows, inner, a8, a8s, st));
+        count_store(e, 0);
+        ProbeScope ps(e, KC_OUT, st, &c.site, &g.probe);
+        KCK(gemm_mx8(epi_resid, g, mx_ops(Ly.out), st));
+      } else {
+        gemm_policy(c, g, epi_resid, KC_OUT);
+        ProbeScope ps(e, KC_OUT, st, &c.site, &g.probe);
+        KCK(gemm(bf, epi_resid, g, st));
+      }
     }
     if (!fold_on && !rms_on) {
       ProbeScope ps(e, KC_NORM, st, &c.site);
       if (dit) {
-        if (do_ln) KCK(ln_modulate(bf, h, r16, rows, d, ad + 3 * d /*shift_mlp*/, ad + 4 * d /*scale_mlp*/, aop, st));
+        if (do_ln && (mx & kStoreBit(KC_FFN1)))
+          KCK(ln_modulate_mx8(h, r16, rows, d, ad + 3 * d /*shift_mlp*/, ad + 4 * d /*scale_mlp*/, a8, a8s, st));
+        else if (do_ln)
+          KCK(ln_modulate(bf, h, r16, rows, d, ad + 3 * d /*shift_mlp*/, ad + 4 * d /*scale_mlp*/, aop, st));
       }
       else
         KCK(rms_norm_g(bf, h, r16, rows, d, Ly.g_ff, aop, st));
@@ -628,9 +663,15 @@ static int backbone_part(Ctx& c, int s0, int ns, hipStream_t st) {
         g.W = Ly.ff1_g.w;
         rms_consumer(g);
       }
-      gemm_policy(c, g, EPI_GELU_TANH, KC_FFN1);
-      ProbeScope ps(e, KC_FFN1, st, &c.site, &g.probe);
-      KCK(gemm(bf, EPI_GELU_TANH, g, st));
+      if (mx & kStoreBit(KC_FFN1)) {
+        count_store(e, 0);
+        ProbeScope ps(e, KC_FFN1, st, &c.site, &g.probe);
+        KCK(gemm_mx8(EPI_GELU_TANH, g, mx_ops(Ly.ff1), st));
+      } else {
+        gemm_policy(c, g, EPI_GELU_TANH, KC_FFN1);
+        ProbeScope ps(e, KC_FFN1, st, &c.site, &g.probe);
+        KCK(gemm(bf, EPI_GELU_TANH, g, st));
+      }
     }
     {
       GemmArgs g = gargs(f, a.ff_dim, Ly.ff2, rows, h, d);
@@ -638,9 +679,16 @@ static int backbone_part(Ctx& c, int s0, int ns, hipStream_t st) {
       // the next layer's attention-norm: hs = h (1 + scale_msa of layer l + 1) for its QKV
       if (fold_on && l + 1 < a.depth) fold_producer(g, ada_k + (size_t)(l + 1) * 6 * d + d);
       if (rms_on && l + 1 < a.depth / 2) rms_producer(g);  // the next layer's attention-norm (its input is this h)
-      gemm_policy(c, g, epi_resid, KC_FFN2);
-      ProbeScope ps(e, KC_FFN2, st, &c.site, &g.probe);
-      KCK(gemm(bf, epi_resid, g, st));
+      if (mx & kStoreBit(KC_FFN2)) {
+        KCK(quant_rows_mx8(f, rows, a.ff_dim, a8, a8s, st));
+        count_store(e, 0);
+        ProbeScope ps(e, KC_FFN2, st, &c.site, &g.probe);
+        KCK(gemm_mx8(epi_resid, g, mx_ops(Ly.ff2), st));
+      } else {
+        gemm_policy(c, g, epi_resid, KC_FFN2);
+        ProbeScope ps(e, KC_FFN2, st, &c.site, &g.probe);
+        KCK(gemm(bf, epi_resid, g, st));
+      }
     }
   }
   if (dit) {
@@ -931,6 +979,7 @@ static GraphKey graph_key(const Ctx& c, const void* ws, int kind) {
   key.batch_mask = c.batch_mask + c.isolate;
   key.lnfold = c.lnfold;
   key.store = c.store;
+  key.mx8 = c.mx8;
   key.method = c.method;
   key.rag_B = c.rag_B;
   key.rag_L = c.rag_L;
@@ -1085,8 +1134,10 @@ static int call_begin(f5h_engine* e, hipStream_t st, const CallShape& sh, void* 
   RC(check_ws(c, ws, bytes));
   RC(chain_fault_check(e, c.st));
   // ragged: no chain and no fold, as for every masked batch (each utterance then has the bits of its own unfolded call)
-  c.chain = rg ? 0 : chain_for_call(e, c, ticket);
-  c.lnfold = !rg && e->lnfold && !c.chain && ((e->lnf_ok && !c.batch_mask) || e->rmsf_ok);
+  // F5H_MXFP8 with any class on MX8 operands: no chain and no fold either (mask 0 is the bf16 mode, with both)
+  c.mx8 = e->mx8 ? e->mx8_mask : 0;
+  c.chain = (rg || c.mx8) ? 0 : chain_for_call(e, c, ticket);
+  c.lnfold = !rg && !c.mx8 && e->lnfold && !c.chain && ((e->lnf_ok && !c.batch_mask) || e->rmsf_ok);
   c.store = e->store_policy;
   return 0;
 }

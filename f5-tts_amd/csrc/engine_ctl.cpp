@@ -129,6 +129,30 @@ int f5h_store_policy_stats(f5h_engine* e, int64_t* write_through, int64_t* plain
   return 0;
 }
 
+int f5h_set_mx8_classes(f5h_engine* e, int32_t mask) {
+  if (!e) return fail(F5H_EINVAL, "null engine");
+  if (!e->mx8) return fail(F5H_EINVAL, "set_mx8_classes: not an F5H_MXFP8 engine");
+  if (mask & ~(1 | 4 | 8 | 16))
+    return fail(F5H_EINVAL, "MX8 class mask: bits 1 (QKV), 4 (out-proj), 8 (FFN1) and 16 (FFN2) only");
+  std::lock_guard<std::mutex> g(e->gm);
+  e->mx8_mask = mask;  // part of the step graph's key: a cached graph of another mask is not replayed
+  return 0;
+}
+
+int f5h_mx8_stats(f5h_engine* e, int32_t* mask, int64_t* launches) {
+  if (!e) return fail(F5H_EINVAL, "null engine");
+  if (mask) *mask = e->mx8 ? e->mx8_mask : 0;
+  if (launches) {
+    unsigned long long n = 0;
+    if (e->mx8_count) {
+      HIPCK(hipSetDevice(e->dev));
+      HIPCK(hipMemcpy(&n, e->mx8_count, sizeof(n), hipMemcpyDeviceToHost));
+    }
+    *launches = (int64_t)n;
+  }
+  return 0;
+}
+
 int f5h_store_policy_force(int32_t mode) {
   if (mode < -1 || mode > 1) return fail(F5H_EINVAL, "forced store policy must be -1 (off), 0 (plain) or 1 (write-through)");
   store_policy_force(mode);

@@ -58,6 +58,10 @@ struct Lin {
   void* w = nullptr;      // [Npad][K] operand dtype
   float* b = nullptr;     // [Npad] fp32 (may be null)
   int N = 0, K = 0, Npad = 0;
+  // F5H_MXFP8 engines, the four per-layer GEMMs' weights: e4m3fn elements [N][K] and E8M0 scales [N][K / 32]
+  // (kernels.h 'MXFP8 operands'), quantised from w on the device at creation; w stays
+  uint8_t* w8 = nullptr;
+  uint8_t* ws = nullptr;
 };
 
 struct CNX {
@@ -92,6 +96,9 @@ struct GraphKey {
   // fix the launch geometry; the lengths themselves live in the workspace's segment tables, not in the key
   int32_t rag_B, rag_L;
   uint32_t cfg_bits;
+  // F5H_MXFP8 engines: the classes that run on MXFP8 operands (f5h_set_mx8_classes; 0 otherwise). spare: always 0,
+  // keeps the struct free of padding
+  int32_t mx8, spare;
 };
 static_assert(std::has_unique_object_representations_v<GraphKey>, "GraphKey is compared as bytes: no padding");
 inline bool operator==(const GraphKey& a, const GraphKey& b) { return std::memcmp(&a, &b, sizeof(GraphKey)) == 0; }
@@ -100,6 +107,10 @@ struct f5h_engine {
   f5h_arch a{};
   int dev = 0;
   int bf = 0;          // compute mode (f5h_compute == ComputeMode): 0 fp32, 1 bf16, 2 fp16 operands
+  // F5H_MXFP8 (DESIGN.md §3 'MXFP8 GEMMs'): bf = 1 throughout, and the per-layer GEMM classes of mx8_mask (kStoreBit:
+  // QKV 1, out-proj 4, FFN1 8, FFN2 16) take MXFP8 operands. mx8_count: device word the MX8 GEMM launches bump
+  int mx8 = 0, mx8_mask = 0;
+  unsigned long long* mx8_count = nullptr;
   size_t esz = 4;      // operand element size
   int tdp = 0;         // text_dim padded to 64
   std::vector<void*> allocs;  // device memory from the stream-ordered pool (dev_alloc), freed by the reaper
@@ -265,6 +276,9 @@ struct Bufs {
   // (sequence, position) table [2R] of the QKV epilogue
   int32_t *rg_off, *rg_len;
   int2* rg_tab;
+  // F5H_MXFP8 engines (null otherwise): the activation operand of the MX8 launches, elements [rows][max K] and
+  // scales [rows][max K / 32] (max K = max(dim, ff_dim); a launch uses the leading rows x K bytes of its part)
+  uint8_t *a8, *a8s;
 };
 
 // ---------------------------------------------------------------- one call
@@ -284,6 +298,7 @@ struct Ctx {
   int chain;  // this call may run the phase chain (engine switch, shape, and chain_admit's per-device check)
   int lnfold;  // this call runs the LayerNorm fold (engine switch, shape; never beside the chain)
   int store;   // the engine's store policy at the start of the call
+  int mx8;     // the engine's MX8 class mask at the start of the call (0: not an F5H_MXFP8 engine)
   double* hp;  // host milliseconds of the call by phase (kHostPhases, f5h_last_call_host_ms), or null
   // ragged sampling (f5h_sample_ragged; rag_B = 0 otherwise): rag_B utterances of at most rag_L frames as packed rows.
   // The row-local launches see B = 1, N = L = R (one "sequence" per CFG branch); the four kernels that reach across

@@ -730,4 +730,183 @@ int f5h_op_scale_cols(void* stream, int32_t compute, int64_t rows, int32_t K, co
   return 0;
 }
 
+// ---------------------------------------------------------------- MXFP8 hooks (kernels.h 'MXFP8 operands')
+int f5h_debug_mx8_quant_block(const float* v32, uint8_t* q32, uint8_t* scale) {
+  if (!v32 || !q32 || !scale) return fail(F5H_EINVAL, "mx8_quant_block: null argument");
+  uint32_t bits[32], amax = 0;
+  std::memcpy(bits, v32, sizeof(bits));
+  for (uint32_t b : bits) amax = std::max(amax, b & 0x7FFFFFFFu);
+  const uint8_t sb = mx8_scale_byte(amax);
+  float mult;
+  const uint32_t mb = mx8_unscale_bits(sb);
+  std::memcpy(&mult, &mb, 4);
+  for (int i = 0; i < 32; ++i) {
+    uint32_t u = bits[i];
+    if ((u & 0x7FFFFFFFu) < 0x7F800000u) {
+      float v;
+      std::memcpy(&v, &u, 4);
+      const volatile float p = v * mult;  // one fp32 multiply by a power of two, as the device's
+      const float pv = p;
+      std::memcpy(&u, &pv, 4);
+    }
+    q32[i] = mx8_e4m3(u);
+  }
+  *scale = sb;
+  return 0;
+}
+
+int f5h_op_quant_mx8(void* stream, int64_t M, int32_t K, const float* x, uint8_t* q, uint8_t* s, void* workspace,
+                     size_t workspace_bytes) {
+  if (M <= 0 || K <= 0 || K % 32 || M * (int64_t)K >= (1ll << 40)) return fail(F5H_EINVAL, "op_quant_mx8 needs M > 0 and K % 32 == 0");
+  if (!x || !q || !s) return fail(F5H_EINVAL, "op_quant_mx8: null tensor");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  OpWs ws(workspace, workspace_bytes);
+  void* xop = ws.take((size_t)M * K * 2);
+  OPWS_CHECK(ws, "op_quant_mx8");
+  HIPCK(f32_to_op(F5H_C_BF16, x, M * K, xop, st));
+  HIPCK(quant_rows_mx8(xop, M, K, q, s, st));
+  return 0;
+}
+
+int f5h_op_ln_modulate_mx8(void* stream, int32_t h16, int32_t M, int32_t d, const float* h, const float* shift,
+                           const float* scale, uint8_t* q, uint8_t* s, void* workspace, size_t workspace_bytes) {
+  if (M <= 0 || d <= 0 || d % 32 || d > 2048) return fail(F5H_EINVAL, "op_ln_modulate_mx8 needs d % 32 == 0 and d <= 2048");
+  if (!h || !shift || !scale || !q || !s) return fail(F5H_EINVAL, "op_ln_modulate_mx8: null tensor");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  OpWs ws(workspace, workspace_bytes);
+  void* hop = h16 ? ws.take((size_t)M * d * 2) : nullptr;
+  OPWS_CHECK(ws, "op_ln_modulate_mx8");
+  if (hop) HIPCK(f32_to_op(F5H_C_BF16, h, (int64_t)M * d, hop, st));
+  HIPCK(ln_modulate_mx8(hop ? hop : (const void*)h, h16 ? 1 : 0, M, d, shift, scale, q, s, st));
+  return 0;
+}
+
+int f5h_op_gemm_mx8(void* stream, const f5h_op_gemm_args* a, uint8_t* a8_out, uint8_t* as_out, uint8_t* w8_out,
+                    uint8_t* ws_out, void* workspace, size_t workspace_bytes) {
+  if (!a) return fail(F5H_EINVAL, "op_gemm_mx8: null args");
+  const int epi = a->epi, M = a->M, N = a->N, K = a->K;
+  if (epi != EPI_QKV && epi != EPI_RESID16 && epi != EPI_GELU_TANH)
+    return fail(F5H_EINVAL, "op_gemm_mx8: the epilogue must be 2 (GELU_TANH), 7 (QKV) or 9 (RESID16)");
+  if (M <= 0 || N <= 0 || K <= 0 || K % 128) return fail(F5H_EINVAL, "op_gemm_mx8 needs K % 128 == 0");
+  if (!a->A || !a->W) return fail(F5H_EINVAL, "op_gemm_mx8: null operand");
+  if (a->A2 || a->add || a->dual_rows || a->live_len || a->ln_part_in || a->ln_part_out || a->hs_scale || a->hs_out ||
+      a->ln_u || a->ln_v || a->ln_rms || a->ln_nparts)
+    return fail(F5H_EINVAL, "op_gemm_mx8: A2, add, live_len and the fold fields have no MX8 form");
+  const bool resid_epi = epi == EPI_RESID16;
+  if ((a->resid || a->gate || a->rowkeep) && !resid_epi)
+    return fail(F5H_EINVAL, "op_gemm_mx8: resid, gate and rowkeep go with EPI_RESID16");
+  const bool rq = a->seg_off != nullptr;
+  int inner = 0;
+  if (rq) {
+    if (epi != EPI_QKV) return fail(F5H_EINVAL, "op_gemm_mx8: seg_off goes with EPI_QKV");
+    if (a->qkv_dst_len <= 0 || a->seq_len != a->qkv_dst_len)
+      return fail(F5H_EINVAL, "op_gemm_mx8: ragged EPI_QKV needs seq_len == qkv_dst_len > 0");
+    RC(op_seg_check("op_gemm_mx8", a->seg_off, a->n_seq, M, a->qkv_dst_len));
+  }
+  if (epi == EPI_QKV) {
+    inner = a->heads * 64;
+    if (a->heads <= 0 || N != 3 * inner || a->seq_len <= 0 || (!rq && M % a->seq_len) || a->rope_heads < 0 ||
+        a->rope_heads > a->heads || !a->q || !a->k || !a->v)
+      return fail(F5H_EINVAL, "op_gemm_mx8: EPI_QKV needs N == 3 * heads * 64, M % seq_len == 0 and q, k, v");
+    if (a->qkv_dst_len != 0 && a->qkv_dst_len < a->seq_len)
+      return fail(F5H_EINVAL, "op_gemm_mx8: qkv_dst_len must be 0 or >= seq_len");
+    if ((a->q_norm_w != nullptr) != (a->k_norm_w != nullptr) || (a->q_norm_w && !(a->qk_norm_eps >= 0.f)))
+      return fail(F5H_EINVAL, "op_gemm_mx8: qk_norm needs q_norm_w, k_norm_w and qk_norm_eps >= 0");
+  } else if (a->qkv_dst_len || a->q_norm_w || a->k_norm_w) {
+    return fail(F5H_EINVAL, "op_gemm_mx8: qkv_dst_len and qk_norm go with EPI_QKV");
+  } else if (!a->C) {
+    return fail(F5H_EINVAL, "op_gemm_mx8: null C");
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t nC = (int64_t)M * N, nA = (int64_t)M * K, nW = (int64_t)N * K;
+  int64_t nqkv = (int64_t)M * inner;
+  if (epi == EPI_QKV && a->qkv_dst_len) {
+    GemmArgs t{};
+    t.M = M;
+    t.heads = a->heads;
+    t.seq_len = a->seq_len;
+    t.qkv_dst_len = a->qkv_dst_len;
+    nqkv = (int64_t)qkv_dst_elems(t, M / a->seq_len);
+  }
+  if (rq) nqkv = (int64_t)a->n_seq * a->heads * a->qkv_dst_len * 64;
+  OpWs ws(workspace, workspace_bytes);
+  void* wop = ws.take((size_t)nW * 2);
+  void* aop = ws.take((size_t)nA * 2);
+  uint8_t* w8 = reinterpret_cast<uint8_t*>(ws.take((size_t)nW));
+  uint8_t* wsc = reinterpret_cast<uint8_t*>(ws.take((size_t)nW / 32));
+  uint8_t* a8 = reinterpret_cast<uint8_t*>(ws.take((size_t)nA));
+  uint8_t* asc = reinterpret_cast<uint8_t*>(ws.take((size_t)nA / 32));
+  void* cop = epi != EPI_QKV ? ws.take((size_t)nC * 2) : nullptr;
+  void* rop = (resid_epi && a->resid) ? ws.take((size_t)nC * 2) : nullptr;
+  void *qop = nullptr, *kop = nullptr, *vop = nullptr;
+  float2* rope = nullptr;
+  if (epi == EPI_QKV) {
+    rope = reinterpret_cast<float2*>(ws.take((size_t)a->seq_len * 32 * sizeof(float2)));
+    qop = ws.take((size_t)nqkv * 2);
+    kop = ws.take((size_t)nqkv * 2);
+    vop = ws.take((size_t)nqkv * 2);
+  }
+  int32_t* rq_off = rq ? reinterpret_cast<int32_t*>(ws.take((size_t)(a->n_seq + 1) * 4)) : nullptr;
+  int2* rq_tab = rq ? reinterpret_cast<int2*>(ws.take((size_t)M * 8)) : nullptr;
+  OPWS_CHECK(ws, "op_gemm_mx8");
+  HIPCK(f32_to_op(F5H_C_BF16, a->W, nW, wop, st));
+  HIPCK(f32_to_op(F5H_C_BF16, a->A, nA, aop, st));
+  HIPCK(quant_rows_mx8(wop, N, K, w8, wsc, st));
+  HIPCK(quant_rows_mx8(aop, M, K, a8, asc, st));
+  GemmArgs g{};
+  g.M = M;
+  g.N = N;
+  g.K = K;
+  g.bias = a->bias;
+  g.ldc = N;
+  g.gate = a->gate;
+  g.rowkeep = a->rowkeep;
+  if (rq) {
+    HIPCK(seg_upload(a->seg_off, a->n_seq + 1, rq_off, st));
+    HIPCK(build_rowtab(rq_off, a->n_seq, M, rq_tab, nullptr, st));
+    g.add = reinterpret_cast<const float*>(rq_tab);
+  }
+  if (cop) {
+    if (resid_epi) HIPCK(f32_to_op(F5H_C_BF16, a->C, nC, cop, st));
+    g.C = cop;
+  }
+  if (rop) {
+    HIPCK(f32_to_op(F5H_C_BF16, a->resid, nC, rop, st));
+    g.resid = rop;
+  }
+  if (epi == EPI_QKV) {
+    HIPCK(rope_table(a->seq_len, rope, st));
+    if (a->rope_out)
+      HIPCK(hipMemcpyAsync(a->rope_out, rope, (size_t)a->seq_len * 32 * sizeof(float2), hipMemcpyDeviceToDevice, st));
+    g.rope = rope;
+    g.seq_len = a->seq_len;
+    g.heads = a->heads;
+    g.rope_heads = a->rope_heads > 0 ? a->rope_heads : a->heads;
+    g.q_scale = a->q_scale;
+    g.q = qop;
+    g.k = kop;
+    g.v = vop;
+    g.q_norm_w = a->q_norm_w;
+    g.k_norm_w = a->k_norm_w;
+    g.qk_norm_eps = a->qk_norm_eps;
+    g.qkv_dst_len = a->qkv_dst_len;
+    // rows the launch does not own (and panel rows past a ragged sequence) come back as the caller's buffers hold them
+    HIPCK(f32_to_op(F5H_C_BF16, a->q, nqkv, qop, st));
+    HIPCK(f32_to_op(F5H_C_BF16, a->k, nqkv, kop, st));
+    HIPCK(f32_to_op(F5H_C_BF16, a->v, nqkv, vop, st));
+  }
+  HIPCK(gemm_mx8(epi, g, Mx8Ops{a8, asc, w8, wsc, nullptr}, st));
+  if (cop) HIPCK(op_to_f32(F5H_C_BF16, cop, nC, a->C, st));
+  if (epi == EPI_QKV) {
+    HIPCK(op_to_f32(F5H_C_BF16, qop, nqkv, a->q, st));
+    HIPCK(op_to_f32(F5H_C_BF16, kop, nqkv, a->k, st));
+    HIPCK(op_to_f32(F5H_C_BF16, vop, nqkv, a->v, st));
+  }
+  if (a8_out) HIPCK(hipMemcpyAsync(a8_out, a8, (size_t)nA, hipMemcpyDeviceToDevice, st));
+  if (as_out) HIPCK(hipMemcpyAsync(as_out, asc, (size_t)nA / 32, hipMemcpyDeviceToDevice, st));
+  if (w8_out) HIPCK(hipMemcpyAsync(w8_out, w8, (size_t)nW, hipMemcpyDeviceToDevice, st));
+  if (ws_out) HIPCK(hipMemcpyAsync(ws_out, wsc, (size_t)nW / 32, hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+
 }  // extern "C"

@@ -408,8 +408,12 @@ static int check_arch(const f5h_arch* a) {
     return fail(F5H_EINVAL, "text_dim must be <= 512, % 4");
   if (a->depth <= 0 || (a->backbone == F5H_UNETT && a->depth % 2)) return fail(F5H_EINVAL, "bad depth");
   if (a->backbone == F5H_UNETT && a->conv_layers != 0) return fail(F5H_EINVAL, "UNetT with conv_layers unsupported");
-  if (a->compute != F5H_FP32 && a->compute != F5H_BF16 && a->compute != F5H_FP16)
-    return fail(F5H_EINVAL, "compute must be FP32, BF16 or FP16");
+  if (a->compute != F5H_FP32 && a->compute != F5H_BF16 && a->compute != F5H_FP16 && a->compute != F5H_MXFP8)
+    return fail(F5H_EINVAL, "compute must be FP32, BF16, FP16 or MXFP8");
+  if (a->compute == F5H_MXFP8) {  // the MX8 GEMM's K-step is 128 elements (dim and heads * 64: checked above)
+    if (a->backbone != F5H_DIT) return fail(F5H_EINVAL, "compute MXFP8: the backbone must be DiT");
+    if (a->ff_dim % 128) return fail(F5H_EINVAL, "compute MXFP8: ff_dim must be a multiple of 128");
+  }
   if (a->qk_norm != 0 && a->qk_norm != 1) return fail(F5H_EINVAL, "qk_norm must be 0 (none) or 1 (rms_norm)");
   if ((a->long_skip_connection != 0 && a->long_skip_connection != 1) ||
       (a->text_average_upsampling != 0 && a->text_average_upsampling != 1))
@@ -446,8 +450,14 @@ int f5h_engine_create_views(const f5h_arch* arch, const f5h_tensor_view* weights
   }
   e->a = *arch;
   e->dev = device;
-  e->bf = arch->compute;
+  // MXFP8 is the bf16 mode with MX8 operands in the per-layer GEMM classes of mx8_mask (default: all four)
+  e->mx8 = arch->compute == F5H_MXFP8 ? 1 : 0;
+  e->bf = e->mx8 ? F5H_BF16 : arch->compute;
   e->esz = e->bf ? 2 : 4;
+  if (e->mx8) {
+    e->mx8_mask = 1 | 4 | 8 | 16;
+    if (const char* mv = getenv("F5H_MX8_CLASSES")) e->mx8_mask = atoi(mv) & (1 | 4 | 8 | 16);
+  }
   // text columns of the hoisted input projection (none for MMDiT: its text is a stream of its own)
   e->tdp = arch->backbone == F5H_MMDIT ? 0 : (arch->text_dim + 63) / 64 * 64;
   if (const char* gv = getenv("F5H_GRAPH")) e->graph_mode = atoi(gv) ? 1 : 0;
@@ -509,6 +519,26 @@ int f5h_engine_create_views(const f5h_arch* arch, const f5h_tensor_view* weights
       for (const Layer& L : e->layers) wp.push_back(L.qkv.w);
       if (upload(e, wp, &e->lnf_w)) e->lnf_ok = false;
     }
+  }
+  // MXFP8: every layer's four GEMM weights quantised on the device from the packed bf16 copy, which stays (a class
+  // outside the mask runs on it), and the device word the MX8 launches count themselves in
+  if (!rc && e->mx8) {
+    for (Layer& L : e->layers) {
+      for (Lin* W : {&L.qkv, &L.out, &L.ff1, &L.ff2}) {
+        void *q8 = nullptr, *s8 = nullptr;
+        if (W->K % 128 || dalloc(e, (size_t)W->N * W->K, &q8) || dalloc(e, (size_t)W->N * (W->K / 32), &s8) ||
+            quant_rows_mx8(W->w, W->N, W->K, (uint8_t*)q8, (uint8_t*)s8, e->mstream) != hipSuccess) {
+          rc = fail(F5H_EHIP, "MXFP8 weight quantisation");
+          break;
+        }
+        W->w8 = (uint8_t*)q8;
+        W->ws = (uint8_t*)s8;
+      }
+      if (rc) break;
+    }
+    void* cw = nullptr;
+    if (!rc && dalloc(e, 64, &cw)) rc = fail(F5H_EHIP, "MXFP8 launch counter");  // (zeroed)
+    e->mx8_count = reinterpret_cast<unsigned long long*>(cw);
   }
   if (!rc && arch->backbone == F5H_MMDIT) e->ada_row = e->ada.Npad;  // no fold: the modulation rows only
   // RMSNorm fold support (UNetT, 16-bit): every layer's QKV and FFN1 weights with their norm's gain folded in

@@ -495,6 +495,58 @@ struct PackArgs {
 };
 hipError_t pack_strided(const PackArgs& a, hipStream_t st);
 
+// ---- MXFP8 operands (OCP MX; compute mode F5H_MXFP8: quant_mx8.hip, gemm_mx8.hip; DESIGN.md §3 'MXFP8 GEMMs').
+// A [rows, K] panel is e4m3fn bytes [rows, K] plus one E8M0 scale byte per 32 consecutive K elements [rows, K / 32];
+// element value = e4m3(byte) * 2^(scale - 127). The quantisation rule is written in integers, the same code on host
+// (f5h_debug_mx8_quant_block, the CPU tests) and device, for weights and activations alike:
+//   amax  = the largest |v| of the block as fp32 bits (an integer maximum: NaN > inf > every finite value)
+//   scale = clamp(E - 8 + (m > 0x600000), 0, 254) with E / m the exponent / mantissa fields of amax,
+//           i.e. 2^ceil(log2(amax / 448)): no element exceeds 448 (the largest e4m3fn value), nothing saturates
+//   elem  = RNE e4m3fn of v * 2^(127 - scale) (an exact multiply); a non-finite v gives the e4m3fn NaN 0x7F
+__host__ __device__ inline uint8_t mx8_scale_byte(uint32_t amax_bits) {
+  const int E = (int)((amax_bits >> 23) & 0xFFu), b = E - 8 + ((amax_bits & 0x7FFFFFu) > 0x600000u ? 1 : 0);
+  return (uint8_t)(b < 0 ? 0 : (b > 254 ? 254 : b));
+}
+// fp32 bits of the scaled value (|x| <= 448 when finite) -> e4m3fn byte, round to nearest even
+__host__ __device__ inline uint8_t mx8_e4m3(uint32_t u) {
+  const uint32_t sign = (u >> 24) & 0x80u;
+  uint32_t a = u & 0x7FFFFFFFu, code;
+  if (a >= 0x7F800000u) return 0x7Fu;
+  if (a >= 0x3C800000u) {  // >= 2^-6: a normal e4m3 value; the rounding carry runs into the exponent field
+    a += 0x7FFFFu + ((a >> 20) & 1u);
+    code = (a >> 20) - (120u << 3);
+    if (code > 0x7Eu) code = 0x7Eu;
+  } else if (a < 0x3A000000u) {  // < 2^-11: below half of the smallest subnormal 2^-9
+    code = 0;
+  } else {  // subnormal target: RNE(|x| 2^9) in 0 .. 8 (8 = the smallest normal's code)
+    const int sh = 14 - ((int)(a >> 23) - 127);  // 21 .. 25
+    const uint32_t m = (a & 0x7FFFFFu) | 0x800000u, q = m >> sh, rem = m & ((1u << sh) - 1u), half = 1u << (sh - 1);
+    code = q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u);
+  }
+  return (uint8_t)(sign | code);
+}
+// 2^(127 - scale) as fp32 bits (scale <= 248 for every fp32 amax, so the factor is a normal number)
+__host__ __device__ inline uint32_t mx8_unscale_bits(uint8_t scale) { return (uint32_t)(254 - (int)scale) << 23; }
+
+// The fp8 operands of a gemm_mx8 launch, its second kernel argument (GemmArgs keeps its size; its A / W / lda / ldw
+// are unused there). count (or null): device word, bumped once per launch (f5h_mx8_stats; exact under graph replay).
+struct Mx8Ops {
+  const uint8_t* a8; const uint8_t* as;  // A [M, K] elements, [M, K / 32] scales
+  const uint8_t* w8; const uint8_t* ws;  // W [N, K] elements, [N, K / 32] scales
+  unsigned long long* count;
+};
+// x: bf16 [M, K], K % 32 == 0 -> q [M, K], s [M, K / 32]
+hipError_t quant_rows_mx8(const void* x, int64_t M, int K, uint8_t* q, uint8_t* s, hipStream_t st);
+// ln_modulate (bf16 output) written as MX8: bit for bit quant_rows_mx8(ln_modulate(h)), it quantises the
+// bf16-rounded value. h: fp32, or bf16 when h16. d % 32 == 0
+hipError_t ln_modulate_mx8(const void* h, int h16, int M, int d, const float* shift, const float* scale, uint8_t* q,
+                           uint8_t* s, hipStream_t st);
+// C = A8 . W8^T on v_mfma_scale_f32_16x16x128_f8f6f4, fp32 accumulation in ascending K, bf16 epilogues EPI_QKV
+// (qk_norm, ragged row table, qkv_dst_len as the bf16 launches), EPI_RESID16 and EPI_GELU_TANH through epi8
+// (gemm_impl.h). K % 128 == 0. One tile configuration (128 x 128, 4 waves), so an output row's bits depend on its own
+// A row only, whatever M and wherever the row sits.
+hipError_t gemm_mx8(int epi, const GemmArgs& a, const Mx8Ops& o, hipStream_t st);
+
 // ---- In-launch phase chain (chain.hip): the row-local seams of a DiT block-step (out-proj -> LayerNorm ->
 // FFN1 -> FFN2 -> LayerNorm -> next QKV) as ONE launch whose phases hand row groups (kChainRows rows) to the
 // next phase through per-group arrival counters (cdna_hip_programming.md §6 Guideline 16, R1: write-through

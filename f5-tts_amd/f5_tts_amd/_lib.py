@@ -20,8 +20,11 @@ LIB_PATH = os.environ.get("F5H_LIB", os.path.join(_HERE, "lib", "libf5h.so"))
 
 F5H_DIT, F5H_UNETT, F5H_MMDIT = 0, 1, 2
 BACKBONE = {"DiT": F5H_DIT, "UNetT": F5H_UNETT, "MMDiT": F5H_MMDIT}
-F5H_FP32, F5H_BF16, F5H_FP16 = 0, 1, 2
-COMPUTE = {"fp32": F5H_FP32, "bf16": F5H_BF16, "fp16": F5H_FP16}
+F5H_FP32, F5H_BF16, F5H_FP16, F5H_MXFP8 = 0, 1, 2, 3
+# "mxfp8": opt-in (never chosen by "auto"): the bf16 mode with MXFP8 operands in the four per-layer DiT GEMMs
+COMPUTE = {"fp32": F5H_FP32, "bf16": F5H_BF16, "fp16": F5H_FP16, "mxfp8": F5H_MXFP8}
+# class bits of f5h_set_mx8_classes (the store policy's)
+MX8_CLASS_BITS = {"qkv": 1, "out": 4, "ffn1": 8, "ffn2": 16}
 F5H_DT_F32, F5H_DT_BF16, F5H_DT_F16 = 0, 1, 2
 F5H_EULER, F5H_MIDPOINT, F5H_RK4 = 0, 1, 2
 ODE_METHOD = {"euler": F5H_EULER, "midpoint": F5H_MIDPOINT, "rk4": F5H_RK4}
@@ -113,6 +116,16 @@ EXPORTS = (
     "f5h_mel_forward_ragged",
     "f5h_last_error",
     "f5h_version",
+)
+
+# the MXFP8 mode's entry points (compute="mxfp8"; tests/test_mx8_host.py checks them against include/f5h.h)
+MX8_EXPORTS = (
+    "f5h_set_mx8_classes",
+    "f5h_mx8_stats",
+    "f5h_debug_mx8_quant_block",
+    "f5h_op_quant_mx8",
+    "f5h_op_ln_modulate_mx8",
+    "f5h_op_gemm_mx8",
 )
 
 KCLASS = {"ffn1": 0, "attention": 1, "qkv": 2, "ffn2": 3, "conv": 4, "out": 5, "norm": 6, "chain": 7}
@@ -339,6 +352,20 @@ def lib():
         L.f5h_store_policy_stats.restype = ctypes.c_int
         L.f5h_store_policy_force.argtypes = [i32]
         L.f5h_store_policy_force.restype = ctypes.c_int
+    if hasattr(L, "f5h_set_mx8_classes"):  # absent from an older build (has_mx8)
+        L.f5h_set_mx8_classes.argtypes = [vp, i32]
+        L.f5h_set_mx8_classes.restype = ctypes.c_int
+        L.f5h_mx8_stats.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i64)]
+        L.f5h_mx8_stats.restype = ctypes.c_int
+        L.f5h_debug_mx8_quant_block.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint8),
+                                                ctypes.POINTER(ctypes.c_uint8)]
+        L.f5h_debug_mx8_quant_block.restype = ctypes.c_int
+        L.f5h_op_quant_mx8.argtypes = [vp, i64, i32, vp, vp, vp, vp, sz]
+        L.f5h_op_quant_mx8.restype = ctypes.c_int
+        L.f5h_op_ln_modulate_mx8.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz]
+        L.f5h_op_ln_modulate_mx8.restype = ctypes.c_int
+        L.f5h_op_gemm_mx8.argtypes = [vp, ctypes.POINTER(OpGemmArgs), vp, vp, vp, vp, vp, sz]
+        L.f5h_op_gemm_mx8.restype = ctypes.c_int
     if hasattr(L, "f5h_chain_debug_spin_limit"):
         L.f5h_chain_debug_spin_limit.argtypes = [i64]
         L.f5h_chain_debug_spin_limit.restype = ctypes.c_int
@@ -452,6 +479,11 @@ def has_ragged_sampler() -> bool:
     """False for an older build (F5H_LIB) without f5h_sample_ragged: such a library has no ragged sampling path
     (CFM.sample(ragged=True)), no ragged op hooks and ignores the seg_off field of the GEMM op hook."""
     return hasattr(lib(), "f5h_sample_ragged")
+
+
+def has_mx8() -> bool:
+    """False for an older build (F5H_LIB) without f5h_set_mx8_classes: such a library has no compute="mxfp8"."""
+    return hasattr(lib(), "f5h_set_mx8_classes")
 
 
 def has_glue_ops() -> bool:

@@ -121,6 +121,22 @@ def _refuse_ragged(arch: dict) -> None:
                            "batches (ragged=True)")
 
 
+def _refuse_mx8(arch: dict) -> None:
+    """compute="mxfp8" serves the DiT backbone with dim, heads * 64 and ff_dim multiples of 128 (the MX8 GEMM's K-step).
+    Everything else is refused before any device work: NotImplementedError for a model the mode does not serve,
+    RuntimeError for an older library (F5H_LIB) without the mode."""
+    if arch["backbone"] != "DiT":
+        raise NotImplementedError(f"compute='mxfp8' serves the DiT backbone only, not {arch['backbone']}")
+    d, inner, ff = arch["dim"], arch["heads"] * arch.get("dim_head", 64), int(arch["dim"] * arch["ff_mult"])
+    for name, val in (("dim", d), ("heads * dim_head", inner), ("ff_dim", ff)):
+        if val % 128:
+            raise NotImplementedError(f"compute='mxfp8' needs {name} to be a multiple of 128, got {val}: the MX8 GEMM "
+                                      "takes K in steps of 128")
+    if not _lib.has_mx8():
+        raise RuntimeError("the loaded libf5h.so has no f5h_set_mx8_classes (an older build): it has no "
+                           "compute='mxfp8'")
+
+
 def _seg_array(seg_off):
     vals = [int(v) for v in seg_off]
     return (ctypes.c_int32 * len(vals))(*vals), vals
@@ -140,6 +156,8 @@ class Engine:
     workspace from the torch caching allocator)."""
 
     def __init__(self, arch: dict, weights: dict, compute: str = "bf16", device=None):
+        if compute == "mxfp8":
+            _refuse_mx8(arch)
         L = _lib.lib()
         self.arch = dict(arch)
         self.compute = compute
@@ -258,6 +276,26 @@ class Engine:
         wt, plain = ctypes.c_int64(), ctypes.c_int64()
         _lib.check(_lib.lib().f5h_store_policy_stats(self._h, ctypes.byref(wt), ctypes.byref(plain)), "store_policy_stats")
         return int(wt.value), int(plain.value)
+
+    def set_mx8_classes(self, classes):
+        """compute="mxfp8" engines: the per-layer GEMM classes that run on MXFP8 operands (f5h_set_mx8_classes): a mask
+        of _lib.MX8_CLASS_BITS, or an iterable of their names. A class left out runs the bf16 mode's launch; none at
+        all is the bf16 mode bit for bit. Default: all four."""
+        if not isinstance(classes, int):
+            classes = sum(_lib.MX8_CLASS_BITS[c] for c in set(classes))
+        if not _lib.has_mx8():
+            raise RuntimeError("the loaded libf5h.so has no f5h_set_mx8_classes (an older build)")
+        _lib.check(_lib.lib().f5h_set_mx8_classes(self._h, int(classes)), "set_mx8_classes")
+
+    def mx8_stats(self):
+        """(the MX8 class mask, MX8 GEMM launches the device has run for this engine, graph replays included).
+        Synchronous; call after the engine's work has completed (f5h_mx8_stats)."""
+        if not _lib.has_mx8():
+            raise RuntimeError("the loaded libf5h.so has no f5h_mx8_stats (an older build)")
+        m, n = ctypes.c_int32(), ctypes.c_int64()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().f5h_mx8_stats(self._h, ctypes.byref(m), ctypes.byref(n)), "mx8_stats")
+        return int(m.value), int(n.value)
 
     def chain_stats(self):
         """(phase-chain launches this engine enqueued, 1 if one of its chain waits gave up and the engine has not
@@ -699,7 +737,7 @@ def op_gemm_epi(epi, A, W, bias=None, C=None, compute="bf16", A2=None, k_split=0
                 live_len=None, live_seq=0, add=None, dual_rows=0, seq_len=0, heads=0, rope_heads=0, q_scale=0.0,
                 hs_scale=None, ln_producer=False, ln_part_in=None, ln_u=None, ln_v=None, ln_rms=False, ln_eps=0.0,
                 ln_nparts=None, poison=False, ws_fill=None, return_ws=False, q_norm_w=None, k_norm_w=None,
-                qk_norm_eps=1e-6, qkv_dst_len=0, qkv_bufs=None, qkv_row0=0, seg_off=None):
+                qk_norm_eps=1e-6, qkv_dst_len=0, qkv_bufs=None, qkv_row0=0, seg_off=None, _mx8=None):
     """A GEMM with epilogue `epi` (a key of EPI; f5h_op_gemm_epi). The in/out epilogues update a copy of C and
     return it; "inproj" returns C [M + dual_rows, N]; "qkv" returns (q, k, v [S,H,L,64], rope [L,32,2]).
 
@@ -799,10 +837,70 @@ def op_gemm_epi(epi, A, W, bias=None, C=None, compute="bf16", A2=None, k_split=0
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     if ws_fill is not None:
         ws.fill_(int(ws_fill))
+    if _mx8 is not None:  # op_gemm_mx8: the same arguments through the MX8 hook, which also returns the operands
+        _lib.check(_lib.lib().f5h_op_gemm_mx8(_lib.stream_handle(dev), ctypes.byref(a), *(t.data_ptr() for t in _mx8),
+                                              ws.data_ptr(), ws.numel()), "f5h_op_gemm_mx8")
+        return out
     _lib.check(_lib.lib().f5h_op_gemm_epi(_lib.stream_handle(dev), ctypes.byref(a), ws.data_ptr(), ws.numel()),
                "f5h_op_gemm_epi")
     res = (out, hs, parts) if ln_producer else out
     return (res, ws) if return_ws else res
+
+
+def _need_mx8():
+    if not _lib.has_mx8():
+        raise RuntimeError("the loaded libf5h.so has no MXFP8 op hooks (an older build)")
+
+
+def op_quant_mx8(x):
+    """quant_rows_mx8 alone (f5h_op_quant_mx8): x [M, K] fp32, rounded to bf16 and quantised on the device. Returns
+    (q [M, K], s [M, K / 32]) uint8: e4m3fn element bytes and E8M0 scale bytes."""
+    _need_mx8()
+    M, K = x.shape
+    x = _f32(x)
+    q = torch.empty(M, K, dtype=torch.uint8, device=x.device)
+    s = torch.empty(M, K // 32, dtype=torch.uint8, device=x.device)
+    ws = torch.empty(M * K * 2 + 512, dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.lib().f5h_op_quant_mx8(_lib.stream_handle(x.device), M, K, x.data_ptr(), q.data_ptr(), s.data_ptr(),
+                                           ws.data_ptr(), ws.numel()), "f5h_op_quant_mx8")
+    return q, s
+
+
+def op_ln_modulate_mx8(h, shift, scale, h16=True):
+    """ln_modulate writing MX8 (f5h_op_ln_modulate_mx8): LayerNorm(h) (1 + scale) + shift, rounded to bf16, quantised.
+    h16: the kernel reads the bf16-rounded h (the 16-bit residual stream). Returns (q [M, d], s [M, d / 32]) uint8."""
+    _need_mx8()
+    M, d = h.shape
+    dev = h.device
+    h, shift, scale = _f32(h, dev), _f32(shift, dev), _f32(scale, dev)
+    q = torch.empty(M, d, dtype=torch.uint8, device=dev)
+    s = torch.empty(M, d // 32, dtype=torch.uint8, device=dev)
+    ws = torch.empty(M * d * 2 + 512, dtype=torch.uint8, device=dev)
+    _lib.check(_lib.lib().f5h_op_ln_modulate_mx8(_lib.stream_handle(dev), int(bool(h16)), M, d, h.data_ptr(),
+                                                 shift.data_ptr(), scale.data_ptr(), q.data_ptr(), s.data_ptr(),
+                                                 ws.data_ptr(), ws.numel()), "f5h_op_ln_modulate_mx8")
+    return q, s
+
+
+def op_gemm_mx8(epi, A, W, **kw):
+    """The MX8 GEMM with epilogue "qkv", "resid16" or "gelu_tanh" (f5h_op_gemm_mx8): op_gemm_epi's arguments and
+    result, A and W rounded to bf16 and quantised on the device. Returns (result, (a8, as, w8, ws)): the quantised
+    operands the product ran on, uint8 [M, K], [M, K / 32], [N, K], [N, K / 32]."""
+    _need_mx8()
+    (M, K), N, dev = A.shape, W.shape[0], A.device
+    ops = (torch.empty(M, K, dtype=torch.uint8, device=dev), torch.empty(M, K // 32, dtype=torch.uint8, device=dev),
+           torch.empty(N, K, dtype=torch.uint8, device=dev), torch.empty(N, K // 32, dtype=torch.uint8, device=dev))
+    return op_gemm_epi(epi, A, W, compute="bf16", _mx8=ops, **kw), ops
+
+
+def mx8_quant_block_host(v32):
+    """One block of 32 fp32 values through the library's quantisation rule on the host (f5h_debug_mx8_quant_block): the
+    code the device kernels run. Returns (32 element bytes, the scale byte)."""
+    _need_mx8()
+    v = (ctypes.c_float * 32)(*[float(x) for x in v32])
+    q, s = (ctypes.c_uint8 * 32)(), ctypes.c_uint8()
+    _lib.check(_lib.lib().f5h_debug_mx8_quant_block(v, q, ctypes.byref(s)), "f5h_debug_mx8_quant_block")
+    return list(q), int(s.value)
 
 
 def op_text_upsample(te, text, seq_len=None, out=None):
@@ -853,7 +951,7 @@ def op_scale_cols(W, g, compute="bf16"):
 # operand dtype comes back as a torch.bfloat16 / torch.float16 tensor. Every output is a view of a buffer that starts
 # as NaN (integers: OP_FILL) and ends in OP_GUARD more such elements: an element the kernel leaves alone comes back as
 # that fill, and op_guard_intact(out) tells whether it wrote past the end.
-OP_TORCH_DTYPE = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
+OP_TORCH_DTYPE = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16, "mxfp8": torch.bfloat16}
 OP_GUARD, OP_FILL = 256, 0x5A
 
 

@@ -118,8 +118,8 @@ class CFM(nn.Module):
         self.sigma = sigma
         self.odeint_kwargs = odeint_kwargs
         self.vocab_char_map = vocab_char_map
-        if compute not in ("auto", "fp32", "bf16", "fp16"):
-            raise ValueError(f"compute must be 'auto', 'fp32', 'bf16' or 'fp16', got {compute!r}")
+        if compute not in ("auto", "fp32", "bf16", "fp16", "mxfp8"):
+            raise ValueError(f"compute must be 'auto', 'fp32', 'bf16', 'fp16' or 'mxfp8', got {compute!r}")
         self.compute = compute
 
     @property
@@ -128,7 +128,8 @@ class CFM(nn.Module):
 
     def engine_compute(self) -> str:
         """"auto": the parameter dtype picks the mode (fp32 -> parity, fp16 -> fp16 MFMA as the reference
-        runs on GPUs, utils_infer.py:190-199; bf16 -> bf16 MFMA); or "fp32" / "bf16" / "fp16" explicitly."""
+        runs on GPUs, utils_infer.py:190-199; bf16 -> bf16 MFMA); or "fp32" / "bf16" / "fp16" explicitly. "mxfp8" is
+        never picked here: callers ask for it (the bf16 mode with MXFP8 operands in the four per-layer DiT GEMMs)."""
         if self.compute != "auto":
             return self.compute
         from .backbones.base import compute_for_dtype

@@ -59,7 +59,14 @@ enum f5h_backbone { F5H_DIT = 0, F5H_UNETT = 1, F5H_MMDIT = 2 };
  *   F5H_BF16: bf16 operands (the BASELINE configs' dtype);
  *   F5H_FP16: fp16 operands = the reference's default GPU dtype (load_checkpoint casts to fp16 on
  *             any GPU with compute capability >= 7, utils_infer.py:190-199); same MFMA rate as bf16. */
-enum f5h_compute { F5H_FP32 = 0, F5H_BF16 = 1, F5H_FP16 = 2 };
+enum f5h_compute { F5H_FP32 = 0, F5H_BF16 = 1, F5H_FP16 = 2, F5H_MXFP8 = 3 };
+/*   F5H_MXFP8 (opt-in, DiT only; DESIGN.md §3 'MXFP8 GEMMs'): the bf16 mode in every respect but the operands of the
+ *             four per-layer GEMMs (QKV, out-projection, FFN1, FFN2), which are OCP MXFP8: e4m3fn elements, one E8M0
+ *             scale byte per 32 consecutive K elements, fp32 accumulation on the block-scaled MFMA. The weights are
+ *             quantised once at creation (beside the bf16 copy), the activations by the LayerNorm launches and by
+ *             quantiser launches ahead of the out-projection and FFN2. f5h_set_mx8_classes chooses the classes.
+ *             Engine creation returns F5H_EINVAL for UNetT, MMDiT and an ff_dim that is not a multiple of 128. The
+ *             LayerNorm fold, the phase chain, the pad-row live_len skip and F5H_RES32 are off in this mode. */
 
 /* Architecture: mirrors DiT.__init__ (dit.py:171-192) / UNetT.__init__ (unett.py:108-129)
  * and the Hydra arch block (configs/F5TTS_v1_Base.yaml:24-37). */
@@ -346,6 +353,14 @@ int f5h_ln_fold_stats(f5h_engine* eng, int32_t* supported, int64_t* passes);
 int f5h_set_store_policy(f5h_engine* eng, int32_t mode);
 int f5h_store_policy_stats(f5h_engine* eng, int64_t* write_through, int64_t* plain);
 int f5h_store_policy_force(int32_t mode);
+/* F5H_MXFP8 engines: the GEMM classes that run on MXFP8 operands, mask of the store policy's class bits (1 QKV,
+ * 4 out-proj, 8 FFN1, 16 FFN2; other bits: F5H_EINVAL). A class outside the mask runs the bf16 launch of the bf16
+ * mode, so mask 0 is that mode bit for bit. Default: all four (29), or F5H_MX8_CLASSES at creation. The mask is part
+ * of the step graph's key. F5H_EINVAL on an engine of another compute mode.
+ * f5h_mx8_stats: *mask = the current mask (0 on other engines), *launches = MX8 GEMM launches the device has run for
+ * this engine (counted on the device, so graph replays count). Synchronous: call after the engine's work completed. */
+int f5h_set_mx8_classes(f5h_engine* eng, int32_t mask);
+int f5h_mx8_stats(f5h_engine* eng, int32_t* mask, int64_t* launches);
 /* Failure of the chain (never expected): a chain wait that gives up (a bounded spin of ~0.3 s) sets the
  * ENGINE's fault word; that call's `out` (f5h_sample) / `pred` (f5h_forward) is then all NaN, and the engine's
  * next f5h_sample / f5h_forward fails with F5H_EHIP (message in f5h_last_error), clears the word and turns the
@@ -517,6 +532,25 @@ typedef struct f5h_op_gemm_args {
 } f5h_op_gemm_args;
 #define F5H_OP_GUARD_ROWS 4
 int f5h_op_gemm_epi(void* stream, const f5h_op_gemm_args* args, void* workspace, size_t workspace_bytes);
+/* MXFP8 op hooks (compute mode F5H_MXFP8). fp32 device tensors in; the hooks round them to bf16 and the DEVICE
+ * quantises: e4m3fn element bytes q [rows, K] and E8M0 scale bytes s [rows, K / 32] come back (device, uint8), value =
+ * e4m3(q) * 2^(s - 127). The rule (integers only): amax = the largest |v| of a 32-block as fp32 bits; s = clamp(E - 8 +
+ * (m > 0x600000), 0, 254) with E, m its exponent and mantissa fields; q = RNE e4m3fn of v * 2^(127 - s); a non-finite v
+ * gives 0x7F. f5h_debug_mx8_quant_block runs the same code on the host for one block of 32 fp32 values.
+ *   f5h_op_quant_mx8: x [M, K], K % 32 == 0.
+ *   f5h_op_ln_modulate_mx8: f5h_op_norm's kind 0 written as MX8 (h16: the kernel reads the bf16-rounded h); bit for bit
+ *     f5h_op_quant_mx8 of f5h_op_norm's output. d % 32 == 0, d <= 2048.
+ *   f5h_op_gemm_mx8: C = A8 . W8^T with epilogue epi 2 (GELU_TANH), 7 (QKV: qk_norm, qkv_dst_len, seg_off as
+ *     f5h_op_gemm_epi) or 9 (RESID16: gate, rowkeep, resid); args->compute is ignored (bf16 epilogues); A2, add,
+ *     live_len and the fold fields are refused. K % 128 == 0. a8 / as / w8 / ws_ (each may be NULL) receive the
+ *     quantised operands [M, K], [M, K / 32], [N, K], [N, K / 32]. */
+int f5h_debug_mx8_quant_block(const float* v32, uint8_t* q32, uint8_t* scale);
+int f5h_op_quant_mx8(void* stream, int64_t M, int32_t K, const float* x, uint8_t* q, uint8_t* s, void* workspace,
+                     size_t workspace_bytes);
+int f5h_op_ln_modulate_mx8(void* stream, int32_t h16, int32_t M, int32_t d, const float* h, const float* shift,
+                           const float* scale, uint8_t* q, uint8_t* s, void* workspace, size_t workspace_bytes);
+int f5h_op_gemm_mx8(void* stream, const f5h_op_gemm_args* args, uint8_t* a8, uint8_t* as, uint8_t* w8, uint8_t* ws_,
+                    void* workspace, size_t workspace_bytes);
 /* The text average upsampling kernel alone (text_average_upsampling): text [B, nt] token ids (-1 = padding),
  * seq_len [B] or NULL (= N): each sequence's frames; in, out [B, N, td] fp32, distinct. Valid tokens are those with
  * id != -1 at positions below min(nt, seq_len[b]); with T of them, base = seq_len / T and rem = seq_len % T, the first
