@@ -119,7 +119,6 @@ static void layout(const f5h_engine* e, WS& ws, Bufs& b, int B, int N, int nfe, 
 }
 
 // ---------------------------------------------------------------- probe
-enum { KC_FFN1 = 0, KC_ATTN = 1, KC_QKV = 2, KC_FFN2 = 3, KC_CONV = 4, KC_OUT = 5, KC_NORM = 6, KC_CHAIN = 7 };
 // Store policy: the class bits of f5h_set_store_policy's per-class form, and the classes the auto rule stores
 // write-through (what the per-class A/B at C2 kept, profiles/r07_ab_store_policy_c2.txt)
 static constexpr int kStoreBit(int kclass) {
@@ -140,18 +139,18 @@ static void gemm_policy(const Ctx& c, GemmArgs& g, int epi, int kclass) {
   g.store_wt = gemm_store_wt(c.e->bf, epi, g, store_want(c.store, kclass));
   count_store(c.e, g.store_wt);
 }
-// Times one launch site when its kernel class is probed. With `kp` the kernel stamps itself
-// (GemmArgs/AttnArgs::probe); without, stamp kernels bracket the launch.
+// Times one launch site when its kernel class is probed (kc < 0: a site that is never timed). With `kp` the kernel
+// stamps itself (GemmArgs/AttnArgs::probe); without, stamp kernels bracket the launch.
 struct ProbeScope {
   f5h_engine* e;
   hipStream_t st;
   bool on;
   bool self = false;
   unsigned long long* slots = nullptr;
-  ProbeScope(f5h_engine* e_, int kc, hipStream_t s, int* site, DevProbe* kp = nullptr)
-      : e(e_), st(s), on(e_->probe_class == kc && e_->pslots && *site < kProbeSites) {
+  ProbeScope(Ctx& c, int kc, hipStream_t s, DevProbe* kp = nullptr)
+      : e(c.e), st(s), on(kc >= 0 && c.m.probe_class == kc && c.e->pslots && c.site < kProbeSites) {
     if (!on) return;
-    const int s0 = (*site)++;
+    const int s0 = c.site++;
     slots = e->pslots + (size_t)s0 * kProbeRow;
     if (kp) {
       self = true;
@@ -219,7 +218,7 @@ static int prologue(Ctx& c, const float* t_host, int nt_vals, const float* cond,
       KCK(silu_to_op(bf, b.temb, b.tin_op, (int64_t)nt_vals * d, st));
       g = gargs(b.tin_op, d, e->ada, nt_vals, b.ada, e->ada_row);
       KCK(gemm(bf, EPI_STORE, g, st));
-      if (c.lnfold) {  // every step's u / v of the folded LayerNorms (kernels.h LnFoldArgs)
+      if (c.m.lnfold) {  // every step's u / v of the folded LayerNorms (kernels.h LnFoldArgs)
         LnFoldArgs la{};
         la.table = b.ada;
         la.stride = e->ada_row;
@@ -330,390 +329,462 @@ static int step_prep(Ctx& c) {
   return 0;
 }
 
-// Sequences [s0, s0+ns) of the packed cond/uncond backbone forward for the current step, enqueued
+// ---------------------------------------------------------------- layer-op launchers
+// Each is the one place for its launch; the backbones differ in the arguments they hand in.
+
+// A part's MX8 activation operand (F5H_MXFP8 engines: elements and scales; null otherwise)
+struct Mx8Act {
+  uint8_t *a8 = nullptr, *a8s = nullptr;
+};
+
+// A per-layer GEMM of class kclass (QKV, out-projection, FFN1, FFN2). With the class's bit in mx it runs on MX8
+// operands: A from act (quantised here from g.A when quant_a: the out-projection and FFN2, whose A no norm launch
+// writes), W's MX8 copy, plain stores only. Otherwise the 16-bit / fp32 launch under the call's store policy.
+static int layer_gemm(Ctx& c, hipStream_t st, int kclass, int epi, GemmArgs& g, const Lin& W, int mx = 0,
+                      const Mx8Act& act = {}, bool quant_a = false) {
+  f5h_engine* e = c.e;
+  if (mx & kStoreBit(kclass)) {
+    // (rows of A the attention's pad-row skip left unwritten quantise to whatever they hold: they feed pad rows of the
+    // product only, which keep their residual)
+    if (quant_a) KCK(quant_rows_mx8(g.A, g.M, g.K, act.a8, act.a8s, st));
+    count_store(e, 0);
+    ProbeScope ps(c, kclass, st, &g.probe);
+    KCK(gemm_mx8(epi, g, Mx8Ops{act.a8, act.a8s, W.w8, W.ws, e->mx8_count}, st));
+  } else {
+    gemm_policy(c, g, epi, kclass);
+    ProbeScope ps(c, kclass, st, &g.probe);
+    KCK(gemm(e->bf, epi, g, st));
+  }
+  return 0;
+}
+
+// The QKV + RoPE GEMM's arguments: A [M, d] into the q / k / v panels, sequences of seq_len rows
+static GemmArgs qkv_gargs(const Ctx& c, const void* A, const Lin& W, int M, int seq_len, void* q, void* k, void* v,
+                          const float* q_norm_w, const float* k_norm_w) {
+  const f5h_arch& a = c.e->a;
+  GemmArgs g = gargs(A, a.dim, W, M, nullptr, 0);
+  g.rope = c.b.rope;
+  g.seq_len = seq_len;
+  g.heads = a.heads;
+  g.rope_heads = a.heads;
+  g.q = q;
+  g.k = k;
+  g.v = v;
+  g.q_scale = 0.125f * 1.4426950408889634f;  // softmax scale 1/sqrt(64) in log2 units, folded into q
+  g.q_norm_w = q_norm_w;  // qk_norm (null without it): RMSNorm of every q / k head ahead of RoPE
+  g.k_norm_w = k_norm_w;
+  g.qk_norm_eps = 1e-6f;  // modules.py:406-407
+  return g;
+}
+
+// Attention over S sequences of L rows. The caller has set what differs between the backbones (kv_len / q_len, the
+// ragged fields, o_split / o2, the second key range).
+static int launch_attention(Ctx& c, hipStream_t st, AttnArgs& at, void* q, void* k, void* v, void* o, int S, int L) {
+  at.q = q;
+  at.k = k;
+  at.v = v;
+  at.o = o;
+  at.S = S;
+  at.H = c.e->a.heads;
+  at.L = L;
+  at.prescaled = 1;
+  at.store_wt = attention_store_wt(c.e->bf, at, store_want(c.store, KC_ATTN));
+  count_store(c.e, at.store_wt);
+  ProbeScope ps(c, KC_ATTN, st, &at.probe);
+  KCK(attention(c.e->bf, at, st));
+  return 0;
+}
+
+// Input embedding of ns sequences from row `no` of the N-row buffers: h0 = y.Wx^T + P, then conv_pos_embed(h0) + h0
+// (two conv_pos launches; rowkeep: their row mask or null) into dst, sequence s at row s * dst_seq_stride + dst_row_off.
+// Sequence s reads y[s % B]; a part holding both branches computes y.Wx^T once and adds both branches' hoisted P rows.
+static int input_embed(Ctx& c, hipStream_t st, int ns, size_t no, const uint8_t* rowkeep, void* dst, int dst_seq_stride,
+                       int dst_row_off) {
+  f5h_engine* e = c.e;
+  Bufs& b = c.b;
+  const int d = e->a.dim, bf = e->bf, BN = c.B * c.N;
+  void* c1 = (char*)b.c1 + no * d * e->esz;
+  GemmArgs g = gargs(b.ypad, 128, e->in_x, BN, b.h0 + no * d, d);
+  g.bias = nullptr;
+  g.add = b.P + no * d;
+  g.ld_add = d;
+  g.dual_rows = ns == 2 * c.B ? BN : 0;
+  KCK(gemm(bf, EPI_INPROJ, g, st));
+  ConvArgs cv{};
+  cv.S = ns;
+  cv.L = c.N;
+  cv.d = d;
+  cv.rowkeep = rowkeep;
+  cv.x = b.h0 + no * d;
+  cv.x_f32 = 1;
+  cv.w = e->conv_w[0];
+  cv.bias = e->conv_b[0];
+  cv.mode = 0;
+  cv.y = c1;
+  if (c.rag_B) {  // packed rows: the part's sequences by the segment table (always the whole packed batch, no == 0)
+    cv.ragged = 1;
+    cv.S = ns * c.rag_B;
+    cv.L = c.rag_L;
+    cv.rowkeep = reinterpret_cast<const uint8_t*>(b.rg_off);
+  }
+  {
+    ProbeScope ps(c, KC_CONV, st);
+    KCK(conv_pos(bf, cv, st));
+  }
+  cv.x = c1;
+  cv.x_f32 = bf ? 0 : 1;
+  cv.w = e->conv_w[1];
+  cv.bias = e->conv_b[1];
+  cv.mode = c.m.r16 ? 2 : 1;
+  cv.y = dst;
+  cv.y_seq_stride = dst_seq_stride;
+  cv.y_row_off = dst_row_off;
+  cv.resid = b.h0 + no * d;
+  KCK(conv_pos(bf, cv, st));
+  return 0;
+}
+
+// LayerNorm + AdaLN modulation in front of a consumer, into the operand that consumer reads: aop, or the MX8 operand
+// when act is given. probed: timed as KC_NORM (the FFN-norm sites; the attention-norm sites never were)
+static int adaln_norm(Ctx& c, hipStream_t st, bool probed, const void* h, int rows, const float* shift,
+                      const float* scale, void* aop, const Mx8Act* act = nullptr) {
+  const int d = c.e->a.dim;
+  ProbeScope ps(c, probed ? KC_NORM : -1, st);
+  KCK(act ? ln_modulate_mx8(h, c.m.r16, rows, d, shift, scale, act->a8, act->a8s, st)
+          : ln_modulate(c.e->bf, h, c.m.r16, rows, d, shift, scale, aop, st));
+  return 0;
+}
+// UNetT's RMSNorm with gain in front of a consumer, probed as adaln_norm
+static int rms_norm(Ctx& c, hipStream_t st, bool probed, const void* h, int rows, const float* gain, void* aop) {
+  ProbeScope ps(c, probed ? KC_NORM : -1, st);
+  KCK(rms_norm_g(c.e->bf, h, c.m.r16, rows, c.e->a.dim, gain, aop, st));
+  return 0;
+}
+
+// The tail: proj_out over the normed rows of aop into b.p from row ro. All Npad (128) columns: the padded weight rows
+// and bias are zero, and whole-column tiles take the fast epilogue; readers use the first mel_dim columns of each row
+static int proj_out_tail(Ctx& c, hipStream_t st, const void* aop, int rows, size_t ro) {
+  f5h_engine* e = c.e;
+  const int pld = e->proj_out.Npad;
+  GemmArgs g = gargs(aop, e->a.dim, e->proj_out, rows, c.b.p + ro * pld, pld);
+  g.N = pld;
+  KCK(gemm(e->bf, EPI_STORE, g, st));
+  return 0;
+}
+
+// ---------------------------------------------------------------- DiT / UNetT
+// One part of a step: sequences [s0, s0 + ns) of the packed batch on stream st, with the part's rows of the buffers
+// the layers share, and the call's modes narrowed to the part
+struct Part {
+  Ctx& c;
+  hipStream_t st;
+  int s0, ns, rows;
+  size_t ro;   // first row of the part (L rows per sequence)
+  size_t hsz;  // element size of the residual stream
+  void *aop, *q, *k, *v, *o, *f;
+  const uint8_t* keep;  // the part's rows of the batch mask, or null
+  Mx8Act act;           // F5H_MXFP8: the activation operand of this part's MX8 launches
+  float* lnp;           // the folds' statistics of the part's rows
+  const float* ada_k;   // DiT: the step's AdaLN table row
+  // chain_on: StepModes::chain_eligible on the whole packed batch. (s0 == 0 only: two chain launches on the two CFG
+  // streams run 72 instead of 49 ms at C2, their waiting workgroups holding the slots the other stream's producers
+  // need, profiles/r05_ab_c2_prio_split.txt; for the same reason the call does not chain while another stream's chained
+  // call is in flight, chain_admit)
+  bool chain_on, fold_on, rms_on;
+  void* res(void* base) const { return (char*)base + ro * c.e->a.dim * hsz; }
+};
+
+static GemmArgs part_qkv_args(const Part& p, const Layer& Lq) {
+  const Ctx& c = p.c;
+  const f5h_arch& a = c.e->a;
+  GemmArgs g = qkv_gargs(c, p.aop, Lq.qkv, p.rows, c.L, p.q, p.k, p.v, Lq.q_norm_w, Lq.k_norm_w);
+  if (a.pe_attn_head > 0) g.rope_heads = a.pe_attn_head;
+  if (c.rag_B) {  // packed rows into padded panels [sequences, H, rag_L, 64] (kernels.h qkv_rowtab)
+    g.add = reinterpret_cast<const float*>(c.b.rg_tab);
+    g.seq_len = c.rag_L;
+    g.qkv_dst_len = c.rag_L;
+  }
+  return g;
+}
+static int part_attention(Part& p) {
+  Ctx& c = p.c;
+  const f5h_arch& a = c.e->a;
+  Bufs& b = c.b;
+  AttnArgs at{};
+  at.kv_len = ((a.attn_mask_enabled || c.isolate) && c.batch_mask) ? b.kvlen + p.s0 : nullptr;
+  // pad query rows' outputs are zeroed after to_out (modules.py:551-553): their blocks are skipped
+  at.q_len = (c.batch_mask && c.m.pad_skip) ? b.kvlen + p.s0 : nullptr;
+  if (!c.rag_B) return launch_attention(c, p.st, at, p.q, p.k, p.v, p.o, p.ns, c.L);
+  // ragged: the sequences' own lengths as key and query lengths; O back to the packed rows
+  at.kv_len = at.q_len = b.rg_len;
+  at.o_split = kAttnRagged;
+  at.o2 = b.rg_off;
+  return launch_attention(c, p.st, at, p.q, p.k, p.v, p.o, p.ns * c.rag_B, c.rag_L);
+}
+// the out-projection's pad-row skip: row tiles of padding only do no work at all (in place only)
+static void live_rows(const Part& p, GemmArgs& g) {
+  g.live_len = p.c.b.kvlen + p.s0;
+  g.live_seq = p.c.L;
+}
+// The folds (DESIGN.md §3 'LayerNorm fold'): a producer GEMM writes its output rows' statistics per 64-column strip,
+// the consumer GEMM applies the norm as algebra. LayerNorm form: the producer also stores hs = h (1 + scale), the
+// consumer takes the step's u / v. RMSNorm form: x / max(|x|, 1e-12) sqrt(d) = x / sqrt(ss / d) (the epsilon only
+// keeps an all-zero row finite), the consumer reads the residual stream itself with W diag(g).
+static void fold_producer(const Part& p, GemmArgs& g, const float* scale) {
+  g.hs = p.aop;
+  g.hs_scale = scale;
+  g.ln_part = p.lnp;
+  g.ln_nparts = p.c.e->a.dim / 64;
+}
+static void fold_consumer(const Part& p, GemmArgs& g, const float* u, const float* v) {
+  g.ln_part_in = p.lnp;
+  g.ln_nparts = p.c.e->a.dim / 64;
+  g.ln_u = u;
+  g.ln_v = v;
+  g.ln_eps = 1e-6f;  // LayerNorm eps (modules.py:316,336)
+}
+static void rms_producer(const Part& p, GemmArgs& g) {
+  g.ln_part = p.lnp;
+  g.ln_nparts = p.c.e->a.dim / 64;
+  g.ln_rms = 1;
+}
+static void rms_consumer(const Part& p, GemmArgs& g, const void* A, const Lin& Wg) {
+  g.A = A;
+  g.W = Wg.w;
+  g.ln_part_in = p.lnp;
+  g.ln_nparts = p.c.e->a.dim / 64;
+  g.ln_rms = 1;
+  g.ln_eps = 1e-30f;
+}
+
+// DiT block l on the stream h, in place (modules.py:743-757). qkv_done: this layer's LayerNorm + QKV came with the
+// previous layer's chain; final_done: the final LayerNorm came with this (the last) layer's chain.
+// In-launch phase chain (chain.hip, Part::chain_on): the out-projection .. FFN2 plus the next layer's LayerNorm + QKV
+// (or the final LayerNorm) as one launch. LayerNorm fold (Part::fold_on): the attention-norm of layers 1.. and every
+// FFN-norm run inside the GEMMs around them; the first layer's attention-norm and the final norm stay launches.
+static int dit_layer(Part& p, int l, void* h, bool& qkv_done, bool& final_done) {
+  Ctx& c = p.c;
+  f5h_engine* e = c.e;
+  const f5h_arch& a = e->a;
+  const StepModes& m = c.m;
+  const int d = a.dim, F = a.ff_dim, inner = a.heads * 64, rows = p.rows;
+  hipStream_t st = p.st;
+  Layer& Ly = e->layers[l];
+  const float* ad = p.ada_k + (size_t)l * 6 * d;  // (shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp)
+  const int epi_resid = m.r16 ? EPI_RESID16 : EPI_RESID;
+  // lnf: layer l's u/v block of the current step's table row (kernels.h LnFoldArgs layout)
+  const float* lnf = p.ada_k + e->ada.Npad + (int64_t)l * (2 * (int64_t)F + 6 * (int64_t)d);
+  auto mx_act = [&](int kclass) { return (m.mx & kStoreBit(kclass)) ? &p.act : nullptr; };
+  if (!qkv_done) {
+    const bool folded = p.fold_on && l > 0;  // the previous layer's FFN2 produced this attention-norm
+    if (m.do_ln && !folded) RC(adaln_norm(c, st, false, h, rows, ad /*shift_msa*/, ad + d /*scale_msa*/, p.aop, mx_act(KC_QKV)));
+    GemmArgs g = part_qkv_args(p, Ly);
+    if (folded) fold_consumer(p, g, lnf + 2 * F, lnf + 2 * F + 3 * d);
+    RC(layer_gemm(c, st, KC_QKV, EPI_QKV, g, Ly.qkv, m.mx, p.act));
+  }
+  qkv_done = false;
+  RC(part_attention(p));
+  if (p.chain_on) {
+    ChainArgs ca{};
+    ca.out = gargs(p.o, inner, Ly.out, rows, h, d);
+    ca.out.gate = ad + 2 * d;  // gate_msa
+    ca.ln1 = LnArgs{h, p.aop, ad + 3 * d /*shift_mlp*/, ad + 4 * d /*scale_mlp*/};
+    ca.ff1 = gargs(p.aop, d, Ly.ff1, rows, p.f, F);
+    ca.ff2 = gargs(p.f, F, Ly.ff2, rows, h, d);
+    ca.ff2.gate = ad + 5 * d;  // gate_mlp
+    if (l + 1 < a.depth) {
+      const float* an = ad + 6 * d;
+      ca.ln2 = LnArgs{h, p.aop, an /*shift_msa*/, an + d /*scale_msa*/};
+      ca.qkv = part_qkv_args(p, e->layers[l + 1]);
+    } else {
+      const float* fin = ad + 6 * d;  // AdaLayerNorm_Final: (scale, shift)
+      ca.ln2 = LnArgs{h, p.aop, fin + d, fin};
+    }
+    ca.cnt = c.b.chain + (size_t)l * 5 * c.b.chain_g4;
+    ca.groups = (rows + kChainRows - 1) / kChainRows;
+    ca.fault = e->chain_fault;
+    ProbeScope ps(c, KC_CHAIN, st, &ca.probe);
+    const hipError_t ce = chain_launch(e->bf, ca, st);
+    if (ce == hipSuccess) {
+      e->n_chain.fetch_add(1, std::memory_order_relaxed);
+      qkv_done = l + 1 < a.depth;
+      final_done = l + 1 == a.depth;
+      return 0;
+    }
+    if (ce != hipErrorInvalidValue) KCK(ce);  // shapes outside the chain: the separate launches below
+  }
+  {
+    GemmArgs g = gargs(p.o, inner, Ly.out, rows, h, d);
+    g.gate = ad + 2 * d;  // gate_msa
+    g.rowkeep = p.keep;   // masked_fill of pad rows (modules.py:552-554)
+    if (m.out_live_skip) live_rows(p, g);
+    if (p.fold_on) fold_producer(p, g, ad + 4 * d /*scale_mlp: hs = h (1 + scale_mlp) for FFN1*/);
+    RC(layer_gemm(c, st, KC_OUT, epi_resid, g, Ly.out, m.mx, p.act, true));
+  }
+  if (!p.fold_on) {
+    if (m.do_ln) {
+      RC(adaln_norm(c, st, true, h, rows, ad + 3 * d /*shift_mlp*/, ad + 4 * d /*scale_mlp*/, p.aop, mx_act(KC_FFN1)));
+    } else {
+      ProbeScope ps(c, KC_NORM, st);  // F5H_DIAG_SKIP_LN: the site keeps its stamps around the skipped launch
+    }
+  }
+  {
+    GemmArgs g = gargs(p.aop, d, Ly.ff1, rows, p.f, F);
+    if (p.fold_on) fold_consumer(p, g, lnf, lnf + F);
+    RC(layer_gemm(c, st, KC_FFN1, EPI_GELU_TANH, g, Ly.ff1, m.mx, p.act));
+  }
+  {
+    GemmArgs g = gargs(p.f, F, Ly.ff2, rows, h, d);
+    g.gate = ad + 5 * d;  // gate_mlp
+    // the next layer's attention-norm: hs = h (1 + scale_msa of layer l + 1) for its QKV
+    if (p.fold_on && l + 1 < a.depth) fold_producer(p, g, ad + 6 * d + d);
+    RC(layer_gemm(c, st, KC_FFN2, epi_resid, g, Ly.ff2, m.mx, p.act, true));
+  }
+  return 0;
+}
+// After the last DiT block: the long skip connection, then the final AdaLN norm of h (or h's projection) into aop
+static int dit_tail(Part& p, void* h, void* hkeep, size_t no, bool final_done) {
+  Ctx& c = p.c;
+  f5h_engine* e = c.e;
+  const f5h_arch& a = e->a;
+  const int d = a.dim;
+  const float* fin = p.ada_k + (size_t)a.depth * 6 * d;  // AdaLayerNorm_Final: (scale, shift)
+  if (hkeep) {
+    // x = long_skip_connection(cat(x, kept)) (dit.py:364-365): ONE GEMM over K = 2d whose A columns [d, 2d) come
+    // from the kept buffer (as the UNetT skip projection), into the free first conv buffer
+    void* hl = (char*)c.b.c1 + no * d * p.hsz;
+    GemmArgs g = gargs(h, d, e->long_skip, p.rows, hl, d);
+    g.A2 = hkeep;
+    g.k_split = d;
+    KCK(gemm(e->bf, c.m.r16 ? EPI_STORE16 : EPI_STORE, g, p.st));
+    h = hl;
+  }
+  if (!final_done) RC(adaln_norm(c, p.st, false, h, p.rows, fin + d, fin, p.aop));
+  return 0;
+}
+
+// UNetT block l (unett.py:280-300); h: the previous layer's output on entry, this layer's on return. RMSNorm fold
+// (Part::rms_on): the FFN-norm of every layer and the attention-norm of layers 1 .. depth/2 - 1 (whose input FFN2 of
+// the previous layer writes) run inside the GEMMs around them. Masked batches too (the producers keep masked rows as
+// they are), but never with the pad-row skip on a producer (StepModes::out_live_skip).
+static int unett_layer(Part& p, int l, void*& h) {
+  Ctx& c = p.c;
+  f5h_engine* e = c.e;
+  const f5h_arch& a = e->a;
+  Bufs& b = c.b;
+  const int d = a.dim, bf = e->bf, inner = a.heads * 64, rows = p.rows, half = a.depth / 2;
+  const bool r16 = c.m.r16;
+  hipStream_t st = p.st;
+  Layer& Ly = e->layers[l];
+  const int epi_resid = r16 ? EPI_RESID16 : EPI_RESID;
+  const void* h_in = nullptr;  // first half: the layer input, kept as its skip connection
+  if (l < half) {
+    // skips.append(x) (unett.py:283-284): layer l reads xs[l] and writes xs[l+1], so xs[l] stays the skip connection
+    // without a copy
+    h_in = p.res(b.xs[l]);
+    h = p.res(b.xs[l + 1]);
+    if (!(p.rms_on && l > 0)) RC(rms_norm(c, st, false, h_in, rows, Ly.g_attn, p.aop));
+  } else {
+    // x = skip_proj(cat(x, skips.pop())) (unett.py:288-297): ONE GEMM over K = 2d whose A columns [d, 2d) come from
+    // the skip buffer; then attention / FFN update the result in place
+    void* x_prev = h;
+    h = p.res(b.pp[(l - half) & 1]);
+    GemmArgs g = gargs(x_prev, d, Ly.skip, rows, h, d);
+    g.A2 = p.res(b.xs[a.depth - 1 - l]);
+    g.k_split = d;
+    KCK(gemm(bf, r16 ? EPI_STORE16 : EPI_STORE, g, st));
+    RC(rms_norm(c, st, false, h, rows, Ly.g_attn, p.aop));
+  }
+  {
+    GemmArgs g = part_qkv_args(p, Ly);
+    if (p.rms_on && l > 0 && l < half) rms_consumer(p, g, h_in, Ly.qkv_g);  // A = the layer input xs[l] itself
+    RC(layer_gemm(c, st, KC_QKV, EPI_QKV, g, Ly.qkv));
+  }
+  RC(part_attention(p));
+  {
+    GemmArgs g = gargs(p.o, inner, Ly.out, rows, h, d);
+    g.resid = h_in;       // first half: x_in + attn(.) -> the next buffer
+    g.rowkeep = p.keep;   // masked_fill of pad rows (modules.py:552-554)
+    // only in place: a first-half layer writes x_in + attn into the next buffer, so its pad rows must still be copied
+    if (c.m.out_live_skip && !h_in) live_rows(p, g);
+    if (p.rms_on) rms_producer(p, g);  // the FFN-norm's statistics of h
+    RC(layer_gemm(c, st, KC_OUT, epi_resid, g, Ly.out));
+  }
+  if (!p.rms_on) RC(rms_norm(c, st, true, h, rows, Ly.g_ff, p.aop));
+  {
+    GemmArgs g = gargs(p.aop, d, Ly.ff1, rows, p.f, a.ff_dim);
+    if (p.rms_on) rms_consumer(p, g, h, Ly.ff1_g);  // A = h itself
+    RC(layer_gemm(c, st, KC_FFN1, EPI_GELU_TANH, g, Ly.ff1));
+  }
+  {
+    GemmArgs g = gargs(p.f, a.ff_dim, Ly.ff2, rows, h, d);
+    if (p.rms_on && l + 1 < half) rms_producer(p, g);  // the next layer's attention-norm (its input is this h)
+    RC(layer_gemm(c, st, KC_FFN2, epi_resid, g, Ly.ff2));
+  }
+  return 0;
+}
+
+// Sequences [s0, s0+ns) of the packed cond/uncond DiT / UNetT forward for the current step, enqueued
 // on `st`; result in b.p rows of those sequences. Every buffer is sequence-major, so a part works on
 // pointer offsets of the packed buffers; sequences never interact, so a part computes exactly what
 // the packed forward computes for its rows (bitwise: GEMM tile configurations agree bit for bit).
 static int backbone_part(Ctx& c, int s0, int ns, hipStream_t st) {
   f5h_engine* e = c.e;
   const f5h_arch& a = e->a;
-  const int d = a.dim, bf = e->bf, H = a.heads, inner = H * 64;
+  const StepModes& m = c.m;
+  const int d = a.dim, inner = a.heads * 64;
   const bool dit = a.backbone == F5H_DIT;
   const size_t es = e->esz;
   Bufs& b = c.b;
-  const int BN = c.B * c.N;
-  const int rows = ns * c.L;
   const size_t ro = (size_t)s0 * c.L;  // first row of the part (L rows per sequence)
   const size_t no = (size_t)s0 * c.N;  // first row in the N-row input-embedding buffers
-  auto op = [&](void* base, size_t row, size_t width) -> void* { return (char*)base + row * width * es; };
-  const uint8_t* keep = c.batch_mask ? b.rowkeep + ro : nullptr;
-  // residual stream: the operand dtype (as the reference keeps it in the parameter dtype), i.e. 16 bit
-  // in the bf16/fp16 modes for DiT and UNetT alike, fp32 in the fp32 parity mode
-  static const bool res32 = [] {  // F5H_RES32=1: fp32 residual on the 16-bit DiT path (A/B)
-    const char* v = getenv("F5H_RES32");
-    return v && *v == '1';
-  }();
-  // F5H_MXFP8 (c.mx8: the classes on MX8 operands; 0 runs the bf16 mode's launches exactly): the activation operand
-  // of this part's MX8 launches, and the launch arguments' second half. With any class on, the residual stream is
-  // 16-bit whatever F5H_RES32 says, and the fold, the chain (call_begin) and the out-projection's live_len skip are off.
-  const int mx = dit ? c.mx8 : 0;
+  auto op = [&](void* base, size_t width) -> void* { return (char*)base + ro * width * es; };
   const size_t mx_kmax = (size_t)std::max(d, a.ff_dim);
-  uint8_t* const a8 = mx ? b.a8 + ro * mx_kmax : nullptr;
-  uint8_t* const a8s = mx ? b.a8s + ro * (mx_kmax / 32) : nullptr;
-  auto mx_ops = [&](const Lin& W) { return Mx8Ops{a8, a8s, W.w8, W.ws, e->mx8_count}; };
-  const bool r16 = bf != 0 && (!dit || !res32 || mx != 0);
-  // F5H_DIAG_SKIP_LN=1: timing-only diagnostic, the 16-bit DiT path skips its LayerNorm launches
-  // (wrong results; bounds what removing those launches can save). Never set in tests or benches.
-  static const bool skip_ln = [] {
-    const char* v = getenv("F5H_DIAG_SKIP_LN");
-    const bool on = v && *v == '1';
-    if (on) std::fprintf(stderr, "[f5h] F5H_DIAG_SKIP_LN=1: LayerNorm launches skipped, results are WRONG (timing only)\n");
-    return on;
-  }();
-  const bool do_ln = !(skip_ln && r16);
-  const size_t hsz = r16 ? es : sizeof(float);
-  auto res = [&](void* base) -> void* { return (char*)base + ro * d * hsz; };
-  void* bh = dit ? res(b.h) : res(b.xs[0]);
-  void* aop = op(b.aop, ro, d);
-  void* q = op(b.q, ro, inner);
-  void* k = op(b.k, ro, inner);
-  void* v = op(b.v, ro, inner);
-  void* o = op(b.o, ro, inner);
-  void* f = op(b.f, ro, a.ff_dim);
-  // ---- input embedding: h0 = y.Wx^T + P, conv position embedding. Sequence s reads y[s % B]; a
-  // part holding both branches computes y.Wx^T once and adds both branches' hoisted P rows.
-  {
-    GemmArgs g = gargs(b.ypad, 128, e->in_x, BN, b.h0 + no * d, d);
-    g.bias = nullptr;
-    g.add = b.P + no * d;
-    g.ld_add = d;
-    g.dual_rows = ns == 2 * c.B ? BN : 0;
-    KCK(gemm(bf, EPI_INPROJ, g, st));
-    ConvArgs cv{};
-    cv.S = ns;
-    cv.L = c.N;
-    cv.d = d;
-    // UNetT's InputEmbedding passes no mask (unett.py:100); isolated, its N audio rows are masked as DiT's are
-    cv.rowkeep = dit ? keep : (c.isolate ? b.rowkeep_n + no : nullptr);
-    cv.x = b.h0 + no * d;
-    cv.x_f32 = 1;
-    cv.w = e->conv_w[0];
-    cv.bias = e->conv_b[0];
-    cv.mode = 0;
-    cv.y = op(b.c1, no, d);
-    if (c.rag_B) {  // packed rows: the part's sequences by the segment table (always the whole packed batch, s0 == 0)
-      cv.ragged = 1;
-      cv.S = ns * c.rag_B;
-      cv.L = c.rag_L;
-      cv.rowkeep = reinterpret_cast<const uint8_t*>(b.rg_off);
-    }
-    {
-      ProbeScope ps(e, KC_CONV, st, &c.site);
-      KCK(conv_pos(bf, cv, st));
-    }
-    cv.x = op(b.c1, no, d);
-    cv.x_f32 = bf ? 0 : 1;
-    cv.w = e->conv_w[1];
-    cv.bias = e->conv_b[1];
-    cv.mode = r16 ? 2 : 1;
-    cv.y = bh;
-    cv.y_seq_stride = c.L;
-    cv.y_row_off = dit ? 0 : 1;
-    cv.resid = b.h0 + no * d;
-    KCK(conv_pos(bf, cv, st));
-  }
-  if (!dit) KCK(write_time_token(bf, r16, b.temb_cur, ns, c.L, d, bh, st));
+  Part p{c, st, s0, ns, ns * c.L, ro, m.r16 ? es : sizeof(float)};
+  p.aop = op(b.aop, d);
+  p.q = op(b.q, inner);
+  p.k = op(b.k, inner);
+  p.v = op(b.v, inner);
+  p.o = op(b.o, inner);
+  p.f = op(b.f, a.ff_dim);
+  p.keep = c.batch_mask ? b.rowkeep + ro : nullptr;
+  if (m.mx) p.act = Mx8Act{b.a8 + ro * mx_kmax, b.a8s + ro * (mx_kmax / 32)};
+  p.lnp = b.lnp ? b.lnp + ro * (size_t)(d / 64) * 2 : nullptr;
+  p.ada_k = dit ? b.ada_cur : nullptr;
+  p.chain_on = m.chain_eligible && b.chain && s0 == 0 && ns == c.S;
+  p.fold_on = m.fold_on && b.lnp;
+  p.rms_on = m.rms_on && b.lnp;
+  void* h = dit ? p.res(b.h) : p.res(b.xs[0]);  // the layer's output (residual updates land here)
+  // ---- input embedding. UNetT's InputEmbedding passes no mask (unett.py:100); isolated, its N audio rows are masked
+  // as DiT's are
+  RC(input_embed(c, st, ns, no, dit ? p.keep : (c.isolate ? b.rowkeep_n + no : nullptr), h, c.L, dit ? 0 : 1));
+  if (!dit) KCK(write_time_token(e->bf, m.r16, b.temb_cur, ns, c.L, d, h, st));
   // long_skip_connection (dit.py:354-355): the stream as it stands after the input embedding, kept for the whole
   // evaluation (a copy: the layers update the stream in place)
-  void* hkeep = a.long_skip_connection ? (char*)b.hkeep + ro * d * hsz : nullptr;
+  void* hkeep = a.long_skip_connection ? (char*)b.hkeep + ro * d * p.hsz : nullptr;
   if (hkeep) {
-    if (bf != 0 && !r16)
+    if (e->bf != 0 && !m.r16)
       return fail(F5H_EINVAL, "long_skip_connection: F5H_RES32 (fp32 residual under 16-bit operands) is not supported");
-    KCK(hipMemcpyAsync(hkeep, bh, (size_t)rows * d * hsz, hipMemcpyDeviceToDevice, st));
+    KCK(hipMemcpyAsync(hkeep, h, (size_t)p.rows * d * p.hsz, hipMemcpyDeviceToDevice, st));
   }
-
-  const float* ada_k = dit ? b.ada_cur : nullptr;
-  const int epi_resid = r16 ? EPI_RESID16 : EPI_RESID;
-  void* h = bh;             // the layer's output (residual updates land here)
-  const void* h_in = nullptr;  // UNetT first half: the layer input, kept as its skip connection
-  auto qkv_args = [&](const Layer& Lq) {
-    GemmArgs g = gargs(aop, d, Lq.qkv, rows, nullptr, 0);
-    g.rope = b.rope;
-    g.seq_len = c.L;
-    g.heads = H;
-    g.rope_heads = a.pe_attn_head > 0 ? a.pe_attn_head : H;
-    g.q = q;
-    g.k = k;
-    g.v = v;
-    g.q_scale = 0.125f * 1.4426950408889634f;  // softmax scale 1/sqrt(64) in log2 units, folded into q
-    g.q_norm_w = Lq.q_norm_w;  // qk_norm (null without it): RMSNorm of every q / k head ahead of RoPE
-    g.k_norm_w = Lq.k_norm_w;
-    g.qk_norm_eps = 1e-6f;     // modules.py:406-407
-    if (c.rag_B) {  // packed rows into padded panels [sequences, H, rag_L, 64] (kernels.h qkv_rowtab)
-      g.add = reinterpret_cast<const float*>(b.rg_tab);
-      g.seq_len = c.rag_L;
-      g.qkv_dst_len = c.rag_L;
-    }
-    return g;
-  };
-  // In-launch phase chain (chain.hip): a layer's out-proj .. FFN2 plus the next layer's LayerNorm + QKV (or
-  // the final LayerNorm) as one launch. The 16-bit DiT path without row masks (single-utterance calls); not
-  // while a chained class is probed (its launches are timed one by one).
-  // (the packed batch only, s0 == 0: two chain launches on the two CFG streams run 72 instead of 49 ms at C2, their
-  // waiting workgroups holding the slots the other stream's producers need, profiles/r05_ab_c2_prio_split.txt; for
-  // the same reason c.chain is off while another stream's chained call is in flight, chain_admit)
-  const bool chain_on = c.chain && dit && r16 && do_ln && !keep && d == 1024 && b.chain && s0 == 0 && ns == c.S &&
-                        (e->probe_class < 0 || e->probe_class == KC_ATTN || e->probe_class == KC_CONV ||
-                         e->probe_class == KC_CHAIN);
-  static const bool zero_memset = [] {  // F5H_CHAIN_ZERO=memset: the counters zeroed by a memset node (A/B)
-    const char* v = getenv("F5H_CHAIN_ZERO");
-    return v && !strcmp(v, "memset");
-  }();
-  if (chain_on) {
-    if (zero_memset)
-      KCK(hipMemsetAsync(b.chain, 0, (size_t)a.depth * 5 * b.chain_g4 * sizeof(unsigned), st));
+  if (p.chain_on) {  // the chain's arrival counters start every step at zero
+    const int64_t words = (int64_t)a.depth * 5 * b.chain_g4;
+    if (proc_switches().chain_zero_memset)
+      KCK(hipMemsetAsync(b.chain, 0, (size_t)words * sizeof(unsigned), st));
     else
-      KCK(zero_words(b.chain, (int64_t)a.depth * 5 * b.chain_g4, st));
+      KCK(zero_words(b.chain, words, st));
   }
-  bool qkv_done = false;    // this layer's LayerNorm + QKV came with the previous layer's chain
-  bool final_done = false;  // the final LayerNorm came with the last layer's chain
-  // LayerNorm fold (engine.lnfold): the attention-norm of layers 1.. and every FFN-norm run inside the GEMMs around
-  // them; the first layer's attention-norm and the final norm stay launches. lnf(l): layer l's u/v block of the
-  // current step's table row (kernels.h LnFoldArgs layout)
-  const bool fold_on = c.lnfold && dit && r16 && do_ln && !keep && !chain_on && b.lnp && e->lnf_ok;
-  // UNetT RMSNorm fold (engine.rmsf_ok): the FFN-norm of every layer and the attention-norm of layers 1 .. depth/2 - 1
-  // (whose input FFN2 of the previous layer writes) run inside the GEMMs around them; the consumers read the residual
-  // stream as A with W diag(g). Masked batches too (the producers keep masked rows as they are), but never with the
-  // pad-row skip on a producer (a skipped tile would leave its rows' statistics unwritten)
-  const bool rms_on = c.lnfold && !dit && r16 && b.lnp && e->rmsf_ok;
-  const int64_t lnf_lw = 2 * (int64_t)a.ff_dim + 6 * (int64_t)d;
-  auto lnf = [&](int l) { return ada_k + e->ada.Npad + (int64_t)l * lnf_lw; };
-  auto fold_consumer = [&](GemmArgs& g, const float* u, const float* v) {
-    g.ln_part_in = b.lnp + ro * (size_t)(d / 64) * 2;
-    g.ln_nparts = d / 64;
-    g.ln_u = u;
-    g.ln_v = v;
-    g.ln_eps = 1e-6f;  // LayerNorm eps (modules.py:316,336)
-  };
-  // RMSNorm form: x / max(|x|, 1e-12) sqrt(d) = x / sqrt(ss / d) (the epsilon only keeps an all-zero row finite)
-  auto rms_consumer = [&](GemmArgs& g) {
-    g.ln_part_in = b.lnp + ro * (size_t)(d / 64) * 2;
-    g.ln_nparts = d / 64;
-    g.ln_rms = 1;
-    g.ln_eps = 1e-30f;
-  };
-  auto rms_producer = [&](GemmArgs& g) {
-    g.ln_part = b.lnp + ro * (size_t)(d / 64) * 2;
-    g.ln_nparts = d / 64;
-    g.ln_rms = 1;
-  };
-  auto fold_producer = [&](GemmArgs& g, const float* scale) {
-    g.hs = aop;
-    g.hs_scale = scale;
-    g.ln_part = b.lnp + ro * (size_t)(d / 64) * 2;
-    g.ln_nparts = d / 64;
-  };
-  if (fold_on || rms_on) e->n_lnfold.fetch_add(1, std::memory_order_relaxed);
-  for (int l = 0; l < a.depth; ++l) {
-    Layer& Ly = e->layers[l];
-    const float* ad = ada_k ? ada_k + (size_t)l * 6 * d : nullptr;
-    if (!dit) {
-      const int half = a.depth / 2;
-      if (l < half) {
-        // skips.append(x) (unett.py:283-284): layer l reads xs[l] and writes xs[l+1], so xs[l] stays
-        // the skip connection without a copy
-        h_in = res(b.xs[l]);
-        h = res(b.xs[l + 1]);
-        if (!(rms_on && l > 0)) KCK(rms_norm_g(bf, h_in, r16, rows, d, Ly.g_attn, aop, st));
-      } else {
-        // x = skip_proj(cat(x, skips.pop())) (unett.py:288-297): ONE GEMM over K = 2d whose A columns
-        // [d, 2d) come from the skip buffer; then attention/FFN update the result in place
-        void* x_prev = h;
-        h = res(b.pp[(l - half) & 1]);
-        h_in = nullptr;
-        GemmArgs g = gargs(x_prev, d, Ly.skip, rows, h, d);
-        g.A2 = res(b.xs[a.depth - 1 - l]);
-        g.k_split = d;
-        KCK(gemm(bf, r16 ? EPI_STORE16 : EPI_STORE, g, st));
-        KCK(rms_norm_g(bf, h, r16, rows, d, Ly.g_attn, aop, st));
-      }
-    } else {
-      if (do_ln && !qkv_done && !(fold_on && l > 0)) {
-        if (mx & kStoreBit(KC_QKV))
-          KCK(ln_modulate_mx8(h, r16, rows, d, ad /*shift_msa*/, ad + d /*scale_msa*/, a8, a8s, st));
-        else
-          KCK(ln_modulate(bf, h, r16, rows, d, ad /*shift_msa*/, ad + d /*scale_msa*/, aop, st));
-      }
-    }
-    if (!qkv_done) {
-      GemmArgs g = qkv_args(Ly);
-      if (fold_on && l > 0) fold_consumer(g, lnf(l) + 2 * a.ff_dim, lnf(l) + 2 * a.ff_dim + 3 * d);
-      if (rms_on && l > 0 && l < a.depth / 2) {  // A = the layer input xs[l] itself, W diag(g_attn)
-        g.A = h_in;
-        g.W = Ly.qkv_g.w;
-        rms_consumer(g);
-      }
-      if (mx & kStoreBit(KC_QKV)) {
-        count_store(e, 0);  // (the MX8 kernel has plain stores only)
-        ProbeScope ps(e, KC_QKV, st, &c.site, &g.probe);
-        KCK(gemm_mx8(EPI_QKV, g, mx_ops(Ly.qkv), st));
-      } else {
-        gemm_policy(c, g, EPI_QKV, KC_QKV);
-        ProbeScope ps(e, KC_QKV, st, &c.site, &g.probe);
-        KCK(gemm(bf, EPI_QKV, g, st));
-      }
-    }
-    qkv_done = false;
-    {
-      AttnArgs at{};
-      at.q = q;
-      at.k = k;
-      at.v = v;
-      at.o = o;
-      at.S = ns;
-      at.H = H;
-      at.L = c.L;
-      at.kv_len = ((a.attn_mask_enabled || c.isolate) && c.batch_mask) ? b.kvlen + s0 : nullptr;
-      // pad query rows' outputs are zeroed after to_out (modules.py:551-553): their blocks are skipped
-      at.q_len = (c.batch_mask && e->pad_skip) ? b.kvlen + s0 : nullptr;
-      at.prescaled = 1;
-      if (c.rag_B) {  // the sequences' own lengths as key and query lengths; O back to the packed rows
-        at.S = ns * c.rag_B;
-        at.L = c.rag_L;
-        at.kv_len = at.q_len = b.rg_len;
-        at.o_split = kAttnRagged;
-        at.o2 = b.rg_off;
-      }
-      at.store_wt = attention_store_wt(bf, at, store_want(c.store, KC_ATTN));
-      count_store(e, at.store_wt);
-      ProbeScope ps(e, KC_ATTN, st, &c.site, &at.probe);
-      KCK(attention(bf, at, st));
-    }
-    if (chain_on) {
-      ChainArgs ca{};
-      ca.out = gargs(o, inner, Ly.out, rows, h, d);
-      ca.out.gate = ad + 2 * d;  // gate_msa
-      ca.ln1 = LnArgs{h, aop, ad + 3 * d /*shift_mlp*/, ad + 4 * d /*scale_mlp*/};
-      ca.ff1 = gargs(aop, d, Ly.ff1, rows, f, a.ff_dim);
-      ca.ff2 = gargs(f, a.ff_dim, Ly.ff2, rows, h, d);
-      ca.ff2.gate = ad + 5 * d;  // gate_mlp
-      if (l + 1 < a.depth) {
-        const float* an = ada_k + (size_t)(l + 1) * 6 * d;
-        ca.ln2 = LnArgs{h, aop, an /*shift_msa*/, an + d /*scale_msa*/};
-        ca.qkv = qkv_args(e->layers[l + 1]);
-      } else {
-        const float* fin = ada_k + (size_t)a.depth * 6 * d;  // AdaLayerNorm_Final: (scale, shift)
-        ca.ln2 = LnArgs{h, aop, fin + d, fin};
-      }
-      ca.cnt = b.chain + (size_t)l * 5 * b.chain_g4;
-      ca.groups = (rows + kChainRows - 1) / kChainRows;
-      ca.fault = e->chain_fault;
-      ProbeScope ps(e, KC_CHAIN, st, &c.site, &ca.probe);
-      const hipError_t ce = chain_launch(bf, ca, st);
-      if (ce == hipSuccess) {
-        e->n_chain.fetch_add(1, std::memory_order_relaxed);
-        qkv_done = l + 1 < a.depth;
-        final_done = l + 1 == a.depth;
-        continue;
-      }
-      if (ce != hipErrorInvalidValue) KCK(ce);  // shapes outside the chain: the separate launches below
-    }
-    {
-      GemmArgs g = gargs(o, inner, Ly.out, rows, h, d);
-      g.resid = h_in;                      // UNetT first half: x_in + attn(.) -> the next buffer
-      g.gate = ad ? ad + 2 * d : nullptr;  // gate_msa
-      g.rowkeep = keep;                    // masked_fill of pad rows (modules.py:552-554)
-      // row tiles of padding only: no work at all. Only in place (h_in null): a UNetT first-half layer
-      // writes x_in + attn into the next buffer, so its pad rows must still be copied there
-      if (keep && !h_in && e->pad_skip && !rms_on && !mx) {
-        g.live_len = b.kvlen + s0;
-        g.live_seq = c.L;
-      }
-      if (fold_on) fold_producer(g, ad + 4 * d /*scale_mlp: hs = h (1 + scale_mlp) for FFN1*/);
-      if (rms_on) rms_producer(g);  // the FFN-norm's statistics of h
-      if (mx & kStoreBit(KC_OUT)) {
-        // (rows of o the attention's pad-row skip left unwritten quantise to whatever they hold: they feed pad rows
-        // of the product only, which keep their residual)
-        KCK(quant_rows_mx8(o, rows, inner, a8, a8s, st));
-        count_store(e, 0);
-        ProbeScope ps(e, KC_OUT, st, &c.site, &g.probe);
-        KCK(gemm_mx8(epi_resid, g, mx_ops(Ly.out), st));
-      } else {
-        gemm_policy(c, g, epi_resid, KC_OUT);
-        ProbeScope ps(e, KC_OUT, st, &c.site, &g.probe);
-        KCK(gemm(bf, epi_resid, g, st));
-      }
-    }
-    if (!fold_on && !rms_on) {
-      ProbeScope ps(e, KC_NORM, st, &c.site);
-      if (dit) {
-        if (do_ln && (mx & kStoreBit(KC_FFN1)))
-          KCK(ln_modulate_mx8(h, r16, rows, d, ad + 3 * d /*shift_mlp*/, ad + 4 * d /*scale_mlp*/, a8, a8s, st));
-        else if (do_ln)
-          KCK(ln_modulate(bf, h, r16, rows, d, ad + 3 * d /*shift_mlp*/, ad + 4 * d /*scale_mlp*/, aop, st));
-      }
-      else
-        KCK(rms_norm_g(bf, h, r16, rows, d, Ly.g_ff, aop, st));
-    }
-    {
-      GemmArgs g = gargs(aop, d, Ly.ff1, rows, f, a.ff_dim);
-      if (fold_on) fold_consumer(g, lnf(l), lnf(l) + a.ff_dim);
-      if (rms_on) {  // A = h itself, W diag(g_ff)
-        g.A = h;
-        g.W = Ly.ff1_g.w;
-        rms_consumer(g);
-      }
-      if (mx & kStoreBit(KC_FFN1)) {
-        count_store(e, 0);
-        ProbeScope ps(e, KC_FFN1, st, &c.site, &g.probe);
-        KCK(gemm_mx8(EPI_GELU_TANH, g, mx_ops(Ly.ff1), st));
-      } else {
-        gemm_policy(c, g, EPI_GELU_TANH, KC_FFN1);
-        ProbeScope ps(e, KC_FFN1, st, &c.site, &g.probe);
-        KCK(gemm(bf, EPI_GELU_TANH, g, st));
-      }
-    }
-    {
-      GemmArgs g = gargs(f, a.ff_dim, Ly.ff2, rows, h, d);
-      g.gate = ad ? ad + 5 * d : nullptr;  // gate_mlp
-      // the next layer's attention-norm: hs = h (1 + scale_msa of layer l + 1) for its QKV
-      if (fold_on && l + 1 < a.depth) fold_producer(g, ada_k + (size_t)(l + 1) * 6 * d + d);
-      if (rms_on && l + 1 < a.depth / 2) rms_producer(g);  // the next layer's attention-norm (its input is this h)
-      if (mx & kStoreBit(KC_FFN2)) {
-        KCK(quant_rows_mx8(f, rows, a.ff_dim, a8, a8s, st));
-        count_store(e, 0);
-        ProbeScope ps(e, KC_FFN2, st, &c.site, &g.probe);
-        KCK(gemm_mx8(epi_resid, g, mx_ops(Ly.ff2), st));
-      } else {
-        gemm_policy(c, g, epi_resid, KC_FFN2);
-        ProbeScope ps(e, KC_FFN2, st, &c.site, &g.probe);
-        KCK(gemm(bf, epi_resid, g, st));
-      }
-    }
-  }
+  if (p.fold_on || p.rms_on) e->n_lnfold.fetch_add(1, std::memory_order_relaxed);
+  // ---- the layers, then the final norm into aop
   if (dit) {
-    const float* fin = ada_k + (size_t)a.depth * 6 * d;  // AdaLayerNorm_Final: (scale, shift)
-    if (hkeep) {
-      // x = long_skip_connection(cat(x, kept)) (dit.py:364-365): ONE GEMM over K = 2d whose A columns [d, 2d) come
-      // from the kept buffer (as the UNetT skip projection above), into the free first conv buffer
-      void* hl = (char*)b.c1 + no * d * hsz;
-      GemmArgs g = gargs(h, d, e->long_skip, rows, hl, d);
-      g.A2 = hkeep;
-      g.k_split = d;
-      KCK(gemm(bf, r16 ? EPI_STORE16 : EPI_STORE, g, st));
-      h = hl;
-    }
-    if (!final_done) KCK(ln_modulate(bf, h, r16, rows, d, fin + d, fin, aop, st));
+    bool qkv_done = false, final_done = false;
+    for (int l = 0; l < a.depth; ++l) RC(dit_layer(p, l, h, qkv_done, final_done));
+    RC(dit_tail(p, h, hkeep, no, final_done));
   } else {
-    KCK(rms_norm_g(bf, h, r16, rows, d, e->norm_out_g, aop, st));
+    for (int l = 0; l < a.depth; ++l) RC(unett_layer(p, l, h));
+    RC(rms_norm(c, st, false, h, p.rows, e->norm_out_g, p.aop));
   }
-  // all Npad (128) columns: the padded weight rows and bias are zero, and whole-column tiles take the
-  // fast epilogue; readers use the first mel_dim columns of each 128-float row
-  const int pld = e->proj_out.Npad;
-  GemmArgs g = gargs(aop, d, e->proj_out, rows, b.p + ro * pld, pld);
-  g.N = pld;
-  KCK(gemm(bf, EPI_STORE, g, st));
-  return 0;
+  return proj_out_tail(c, st, p.aop, p.rows, ro);
 }
 
 // The MMDiT backbone (mmdit.py:214-262, modules.py:563-705, 763-846) for all S sequences of the current step; result in
@@ -731,70 +802,27 @@ static int backbone_part(Ctx& c, int s0, int ns, hipStream_t st) {
 static int backbone_mmdit(Ctx& c, hipStream_t st) {
   f5h_engine* e = c.e;
   const f5h_arch& a = e->a;
-  const int d = a.dim, bf = e->bf, H = a.heads, inner = H * 64, F = a.ff_dim;
+  const int d = a.dim, H = a.heads, inner = H * 64, F = a.ff_dim;
   const size_t es = e->esz;
   Bufs& b = c.b;
-  const int BN = c.B * c.N, rows = c.S * c.N, crows = c.S * c.nt, Lj = c.N + c.nt;
-  const bool r16 = bf != 0;  // residual streams in the operand dtype (16-bit modes), fp32 in the fp32 mode
+  const int rows = c.S * c.N, crows = c.S * c.nt, Lj = c.N + c.nt;
+  const bool r16 = c.m.r16;  // residual streams in the operand dtype (16-bit modes), fp32 in the fp32 mode
   const int epi_resid = r16 ? EPI_RESID16 : EPI_RESID;
   const uint8_t* keep = c.batch_mask ? b.rowkeep : nullptr;
-  // ---- audio embedding (mmdit.py:75-81): h0 = y.Wx^T + P, then conv_pos_embed(h0) + h0 (no mask there)
-  {
-    GemmArgs g = gargs(b.ypad, 128, e->in_x, BN, b.h0, d);
-    g.bias = nullptr;
-    g.add = b.P;
-    g.ld_add = d;
-    g.dual_rows = c.S == 2 * c.B ? BN : 0;
-    KCK(gemm(bf, EPI_INPROJ, g, st));
-    ConvArgs cv{};
-    cv.S = c.S;
-    cv.L = c.N;
-    cv.d = d;
-    cv.x = b.h0;
-    cv.x_f32 = 1;
-    cv.w = e->conv_w[0];
-    cv.bias = e->conv_b[0];
-    cv.mode = 0;
-    cv.y = b.c1;
-    cv.rowkeep = c.isolate ? keep : nullptr;  // (the reference passes no mask: pad rows bleed 15 frames per conv)
-    {
-      ProbeScope ps(e, KC_CONV, st, &c.site);
-      KCK(conv_pos(bf, cv, st));
-    }
-    cv.x = b.c1;
-    cv.x_f32 = bf ? 0 : 1;
-    cv.w = e->conv_w[1];
-    cv.bias = e->conv_b[1];
-    cv.mode = r16 ? 2 : 1;
-    cv.y = b.h;
-    cv.y_seq_stride = c.N;
-    cv.y_row_off = 0;
-    cv.resid = b.h0;
-    KCK(conv_pos(bf, cv, st));
-  }
+  // ---- audio embedding (mmdit.py:75-81): conv_pos_embed(h0) + h0 (the reference passes no mask there: pad rows bleed
+  // 15 frames per conv; isolated calls mask them)
+  RC(input_embed(c, st, c.S, 0, c.isolate ? keep : nullptr, b.h, c.N, 0));
   // the text stream's start: the conditional rows then the unconditional ones (packed), or the branch asked for
   const char* te0 = r16 ? (const char*)b.c0 : (const char*)b.te;
   const size_t hsz = r16 ? es : sizeof(float);
   const void* c0 = te0 + ((c.S == c.B && c.drop_text) ? (size_t)c.B * c.nt * d * hsz : 0);
   const float* ada_k = b.ada_cur;
+  // one stream's QKV into its rows [row0, row0 + seq) of every joint panel
   auto qkv = [&](const void* A, const Lin& W, int M, int seq, size_t row0, const float* qn, const float* kn) -> int {
-    GemmArgs g = gargs(A, d, W, M, nullptr, 0);
-    g.rope = b.rope;
-    g.seq_len = seq;
+    GemmArgs g = qkv_gargs(c, A, W, M, seq, (char*)b.q + row0 * 64 * es, (char*)b.k + row0 * 64 * es,
+                           (char*)b.v + row0 * 64 * es, qn, kn);
     g.qkv_dst_len = Lj;
-    g.heads = H;
-    g.rope_heads = H;
-    g.q = (char*)b.q + row0 * 64 * es;
-    g.k = (char*)b.k + row0 * 64 * es;
-    g.v = (char*)b.v + row0 * 64 * es;
-    g.q_scale = 0.125f * 1.4426950408889634f;  // softmax scale 1/sqrt(64) in log2 units, folded into q
-    g.q_norm_w = qn;
-    g.k_norm_w = kn;
-    g.qk_norm_eps = 1e-6f;
-    gemm_policy(c, g, EPI_QKV, KC_QKV);
-    ProbeScope ps(e, KC_QKV, st, &c.site, &g.probe);
-    KCK(gemm(bf, EPI_QKV, g, st));
-    return 0;
+    return layer_gemm(c, st, KC_QKV, EPI_QKV, g, W);
   };
   // out-projection or FFN2 of one stream: C += gate (acc + bias) on kept rows, the residual read from `resid` when set
   auto resid_gemm = [&](const void* A, int K, const Lin& W, int M, void* C, const void* resid, const float* gate,
@@ -803,17 +831,11 @@ static int backbone_mmdit(Ctx& c, hipStream_t st) {
     g.resid = resid;
     g.gate = gate;
     g.rowkeep = rk;
-    gemm_policy(c, g, epi_resid, kclass);
-    ProbeScope ps(e, kclass, st, &c.site, &g.probe);
-    KCK(gemm(bf, epi_resid, g, st));
-    return 0;
+    return layer_gemm(c, st, kclass, epi_resid, g, W);
   };
   auto ffn1 = [&](const void* A, const Lin& W, int M, void* out) -> int {
     GemmArgs g = gargs(A, d, W, M, out, F);
-    gemm_policy(c, g, EPI_GELU_TANH, KC_FFN1);
-    ProbeScope ps(e, KC_FFN1, st, &c.site, &g.probe);
-    KCK(gemm(bf, EPI_GELU_TANH, g, st));
-    return 0;
+    return layer_gemm(c, st, KC_FFN1, EPI_GELU_TANH, g, W);
   };
   for (int l = 0; l < a.depth; ++l) {
     Layer& Ly = e->layers[l];
@@ -821,57 +843,36 @@ static int backbone_mmdit(Ctx& c, hipStream_t st) {
     const float* ax = ada_k + mm_ada_x(a, l);  // (shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp)
     const float* ac = ada_k + mm_ada_c(a, l);  // the same, or (scale, shift) in the last block
     const void* c_in = l == 0 ? c0 : b.ch;
-    KCK(ln_modulate(bf, b.h, r16, rows, d, ax, ax + d, b.aop, st));
-    KCK(ln_modulate(bf, c_in, r16, crows, d, last ? ac + d : ac, last ? ac : ac + d, b.caop, st));
+    RC(adaln_norm(c, st, false, b.h, rows, ax, ax + d, b.aop));
+    RC(adaln_norm(c, st, false, c_in, crows, last ? ac + d : ac, last ? ac : ac + d, b.caop));
     RC(qkv(b.aop, Ly.qkv, rows, c.N, 0, Ly.q_norm_w, Ly.k_norm_w));
     RC(qkv(b.caop, Ly.qkv_c, crows, c.nt, (size_t)c.N, Ly.cq_norm_w, Ly.ck_norm_w));
     {
       AttnArgs at{};
-      at.q = b.q;
-      at.k = b.k;
-      at.v = b.v;
-      at.o = b.o;
       at.o2 = b.co;
       at.o_split = c.N;
-      at.S = c.S;
-      at.H = H;
-      at.L = Lj;
       // isolated: the audio keys [0, dur) and the text keys [N, N + text length) of the joint sequence
       if (c.isolate) {
         at.kv_len = b.kvlen;
         at.kv_start2 = c.N;
         at.kv_len2 = b.tlen;
       }
-      at.prescaled = 1;
-      at.store_wt = attention_store_wt(bf, at, store_want(c.store, KC_ATTN));
-      count_store(e, at.store_wt);
-      ProbeScope ps(e, KC_ATTN, st, &c.site, &at.probe);
-      KCK(attention(bf, at, st));
+      RC(launch_attention(c, st, at, b.q, b.k, b.v, b.o, c.S, Lj));
     }
     RC(resid_gemm(b.o, inner, Ly.out, rows, b.h, nullptr, ax + 2 * d, keep, KC_OUT));
     if (!last) RC(resid_gemm(b.co, inner, Ly.out_c, crows, b.ch, l == 0 ? c0 : nullptr, ac + 2 * d, b.ckeep, KC_OUT));
-    {
-      ProbeScope ps(e, KC_NORM, st, &c.site);
-      KCK(ln_modulate(bf, b.h, r16, rows, d, ax + 3 * d, ax + 4 * d, b.aop, st));
-    }
+    RC(adaln_norm(c, st, true, b.h, rows, ax + 3 * d, ax + 4 * d, b.aop));
     RC(ffn1(b.aop, Ly.ff1, rows, b.f));
     RC(resid_gemm(b.f, F, Ly.ff2, rows, b.h, nullptr, ax + 5 * d, nullptr, KC_FFN2));
     if (!last) {
-      {
-        ProbeScope ps(e, KC_NORM, st, &c.site);
-        KCK(ln_modulate(bf, b.ch, r16, crows, d, ac + 3 * d, ac + 4 * d, b.caop, st));
-      }
+      RC(adaln_norm(c, st, true, b.ch, crows, ac + 3 * d, ac + 4 * d, b.caop));
       RC(ffn1(b.caop, Ly.ff1_c, crows, b.cf));
       RC(resid_gemm(b.cf, F, Ly.ff2_c, crows, b.ch, nullptr, ac + 5 * d, nullptr, KC_FFN2));
     }
   }
   const float* fin = ada_k + mm_ada_fin(a);  // AdaLayerNorm_Final: (scale, shift)
-  KCK(ln_modulate(bf, b.h, r16, rows, d, fin + d, fin, b.aop, st));
-  const int pld = e->proj_out.Npad;
-  GemmArgs g = gargs(b.aop, d, e->proj_out, rows, b.p, pld);
-  g.N = pld;
-  KCK(gemm(bf, EPI_STORE, g, st));
-  return 0;
+  RC(adaln_norm(c, st, false, b.h, rows, fin + d, fin, b.aop));
+  return proj_out_tail(c, st, b.aop, rows, 0);
 }
 
 // One packed cond/uncond backbone forward for the current step; result in b.p [S, L, mel]. With a
@@ -977,9 +978,9 @@ static GraphKey graph_key(const Ctx& c, const void* ws, int kind) {
   key.nfe = c.nfe;
   key.use_cfg = c.use_cfg;
   key.batch_mask = c.batch_mask + c.isolate;
-  key.lnfold = c.lnfold;
+  key.lnfold = c.m.lnfold;
   key.store = c.store;
-  key.mx8 = c.mx8;
+  key.mx8 = c.m.mx;
   key.method = c.method;
   key.rag_B = c.rag_B;
   key.rag_L = c.rag_L;
@@ -1069,12 +1070,11 @@ static int run_steps(Ctx& c, const f5h_sample_args* a, const void* ws) {
   GraphKey key = graph_key(c, ws, 0);
   // MMDiT: the step's launches and the text stream's buffers depend on nt (the other backbones' steps do not)
   if (e->a.backbone != F5H_MMDIT) key.nt = 0;
-  key.probe = e->probe_class;
-  // auto (2): one packed chain. Ragged: always one chain (the segment tables address the packed batch as a whole)
-  const bool split = e->split_cfg == 1 && !c.rag_B;
+  const bool split = c.m.split != 0;
+  key.probe = c.m.probe_class;
   key.split = split;
-  key.pad_skip = e->pad_skip;
-  key.chain = c.chain;
+  key.pad_skip = c.m.pad_skip;
+  key.chain = c.m.chain_call;
   std::memcpy(&key.cfg_bits, &a->cfg_strength, 4);
   std::shared_ptr<GraphEntry> hold;  // keeps the replayed graph alive through the launch loop
   RC(graph_get(c, key, split, [&](Ctx& cc) { return enqueue_step(cc, a); }, hold, c.nfe));
@@ -1133,11 +1133,18 @@ static int call_begin(f5h_engine* e, hipStream_t st, const CallShape& sh, void* 
   RC(check_mmdit_call(e, c.nt, c.batch_mask, c.isolate));
   RC(check_ws(c, ws, bytes));
   RC(chain_fault_check(e, c.st));
-  // ragged: no chain and no fold, as for every masked batch (each utterance then has the bits of its own unfolded call)
-  // F5H_MXFP8 with any class on MX8 operands: no chain and no fold either (mask 0 is the bf16 mode, with both)
-  c.mx8 = e->mx8 ? e->mx8_mask : 0;
-  c.chain = (rg || c.mx8) ? 0 : chain_for_call(e, c, ticket);
-  c.lnfold = !rg && !c.mx8 && e->lnfold && !c.chain && ((e->lnf_ok && !c.batch_mask) || e->rmsf_ok);
+  // the call's modes, from the engine's switches as they stand now; a chain the per-device gate does not admit
+  // (chain_admit: a runtime answer, so not step_modes' business) is a chain switched off
+  const ProcSwitches& ps = proc_switches();
+  ModeIn in{e->a.backbone, e->a.dim, e->a.qk_norm, e->a.long_skip_connection, e->bf,
+            e->lnf_ok, e->rmsf_ok, e->chain_fault != nullptr, e->mx8,
+            e->chain, e->lnfold, e->pad_skip, e->graph_mode, e->split_cfg, e->mx8_mask, e->probe_class,
+            ps.res32, ps.skip_ln, c.use_cfg, c.batch_mask, rg != nullptr};
+  c.m = step_modes(in);
+  if (c.m.chain_call && !chain_for_call(e, c, ticket)) {
+    in.chain = 0;
+    c.m = step_modes(in);
+  }
   c.store = e->store_policy;
   return 0;
 }
@@ -1213,8 +1220,8 @@ static int sample_impl(f5h_engine* e, void* stream, const f5h_sample_args* a, in
   RC(run_steps(c, a, workspace));
   const double h3 = host_ms();
   HIPCK(final_where_out(a->cond, a->cond_mask, c.b.y, a->out, c.B, c.N, e->a.mel_dim,
-                        c.chain ? e->chain_fault : nullptr, c.st));
-  if (c.chain) RC(chain_fault_note(e, c.st));
+                        c.m.chain_call ? e->chain_fault : nullptr, c.st));
+  if (c.m.chain_call) RC(chain_fault_note(e, c.st));
   const double h4 = host_ms();
   hp[HP_TOTAL] = h4 - h0;
   hp[HP_PROLOGUE] = h1 - h0;
@@ -1333,9 +1340,9 @@ int f5h_forward(f5h_engine* e, void* stream, const f5h_forward_args* a, void* wo
     // a kept workspace is reused call after call (the reference's ODE loop over the plugin): the
     // backbone step (workspace buffers only) replays as one graph per (workspace, shape)
     GraphKey key = graph_key(c, workspace, 2);
-    key.probe = e->probe_class;
-    key.pad_skip = e->pad_skip;
-    key.chain = c.chain;
+    key.probe = c.m.probe_class;
+    key.pad_skip = c.m.pad_skip;
+    key.chain = c.m.chain_call;
     key.drop_text = e->a.backbone == F5H_MMDIT ? c.drop_text : 0;
     std::shared_ptr<GraphEntry> hold;
     RC(graph_get(c, key, false, body, hold, 1));
@@ -1345,8 +1352,8 @@ int f5h_forward(f5h_engine* e, void* stream, const f5h_forward_args* a, void* wo
     RC(body(c));
   }
   HIPCK(copy_pred(c.b.p, c.S, c.L, adaln_bb(e->a) ? 0 : 1, e->a.mel_dim, e->proj_out.Npad, a->pred,
-                  c.chain ? e->chain_fault : nullptr, c.st));
-  if (c.chain) RC(chain_fault_note(e, c.st));
+                  c.m.chain_call ? e->chain_fault : nullptr, c.st));
+  if (c.m.chain_call) RC(chain_fault_note(e, c.st));
   return 0;
 }
 

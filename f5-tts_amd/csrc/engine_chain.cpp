@@ -82,24 +82,13 @@ static void chain_leave(int dev, hipStream_t st) {
 ChainTicket::~ChainTicket() {
   if (held) chain_leave(dev, st);
 }
-// Could this call's step run the chain? (the engine switch and the shapes backbone_part checks per part); if so,
-// ask the gate.
-int chain_for_call(f5h_engine* e, const Ctx& c, ChainTicket& t) {
-  static const bool res32 = [] {
-    const char* v = getenv("F5H_RES32");
-    return v && *v == '1';
-  }();
-  const bool split = e->graph_mode && e->split_cfg == 1 && c.use_cfg;  // the two CFG parts: no chain
-  // qk_norm / long_skip_connection: the chain's own QKV phase has no norm and its last launch carries the final
-  // LayerNorm, which the long skip projection must precede: such engines always take the separate launches
-  if (!e->chain || e->a.backbone != F5H_DIT || e->bf == 0 || res32 || e->a.dim != 1024 || c.batch_mask || split ||
-      !e->chain_fault || e->a.qk_norm || e->a.long_skip_connection)
-    return 0;
-  if (!chain_admit(e->dev, c.st)) return 0;
+// A call whose modes allow the chain (StepModes::chain_call) asks the gate; admitted, it holds the ticket.
+bool chain_for_call(f5h_engine* e, const Ctx& c, ChainTicket& t) {
+  if (!c.m.chain_call || !chain_admit(e->dev, c.st)) return false;
   t.dev = e->dev;
   t.st = c.st;
   t.held = true;
-  return 1;
+  return true;
 }
 // Start of every sample/forward call: a give-up recorded by an earlier chained call of this engine (its copy in the
 // pinned word, landed once that call completed) fails this call and switches the chain off for the engine.

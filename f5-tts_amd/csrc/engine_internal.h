@@ -1,8 +1,12 @@
 // Internal header of the engine's translation units (not installed, not part of include/f5h.h).
 //
 // Where things live:
-//   engine.cpp        workspace layout, prologue, backbone (DiT / UNetT / MMDiT), the NFE step and loop, call setup
-//                     (call_begin), graph keys, f5h_sample*, f5h_workspace_size*, f5h_forward, store_want, ProbeScope
+//   engine.cpp        workspace layout, prologue, the layer-op launchers (layer_gemm, launch_attention, input_embed,
+//                     adaln_norm / rms_norm, proj_out_tail), the backbones (dit_layer / unett_layer under backbone_part,
+//                     backbone_mmdit), the NFE step and loop, call setup (call_begin), graph keys, f5h_sample*,
+//                     f5h_workspace_size*, f5h_forward, store_want, ProbeScope
+//   engine_modes.cpp  which modes a call runs in: step_modes (pure, the one place a mode is switched on or off),
+//                     proc_switches (the process-wide environment diagnostics), f5h_debug_step_modes
 //   engine_pack.cpp   weight views and packing (pack_all, pack_mmdit, pack_conv_weight), check_arch,
 //                     f5h_engine_create*, f5h_engine_destroy
 //   engine_graph.cpp  the hipGraph cache: graph_get, reap_graphs, note_replays, prologue_repeats, g_kernel_epoch
@@ -281,6 +285,49 @@ struct Bufs {
   uint8_t *a8, *a8s;
 };
 
+// kernel classes of the launch probes (f5h_probe_enable) and, by kStoreBit, of the store policy and the MX8 mask
+enum { KC_FFN1 = 0, KC_ATTN = 1, KC_QKV = 2, KC_FFN2 = 3, KC_CONV = 4, KC_OUT = 5, KC_NORM = 6, KC_CHAIN = 7 };
+
+// ---------------------------------------------------------------- the modes of one call
+// What step_modes decides from: all int32 (f5h_debug_step_modes takes them as a flat array in this order).
+struct ModeIn {
+  int32_t backbone, dim, qk_norm, long_skip;  // architecture (f5h_arch)
+  int32_t bf;                                 // compute mode (f5h_engine::bf)
+  // engine capabilities: the LayerNorm / RMSNorm fold is supported, the chain's fault word exists, F5H_MXFP8 engine
+  int32_t lnf_ok, rmsf_ok, chain_slot, mx8_engine;
+  // engine switches at the start of the call
+  int32_t chain, lnfold, pad_skip, graph_mode, split_cfg, mx8_mask, probe_class;
+  int32_t res32, skip_ln;              // process-wide diagnostics (proc_switches)
+  int32_t use_cfg, batch_mask, ragged;  // call shape
+};
+// The modes of one call: decided once (call_begin), read by the graph key, the prologue and the backbone. A new mode is
+// a member here and a line in step_modes, where it is also switched off beside the modes it cannot run with. All int32
+// (f5h_debug_step_modes returns them as a flat array in this order).
+struct StepModes {
+  int32_t mx;     // the GEMM classes on MX8 operands (kStoreBit mask; 0: the 16-bit launches exactly)
+  int32_t r16;    // 16-bit residual stream (fp32 in the fp32 mode and, on DiT without MX8 classes, under F5H_RES32=1)
+  int32_t do_ln;  // 0: F5H_DIAG_SKIP_LN=1 skips the 16-bit DiT path's LayerNorm launches (wrong results, timing only)
+  int32_t split;  // the two CFG branches as parallel captured chains (f5h_sample's step graph)
+  // this call may run the phase chain: engine switch, architecture and shape; call_begin then asks chain_admit, whose
+  // refusal acts as the switch being off. Part of the graph key; the fold yields to it
+  int32_t chain_call;
+  // ... and the step's launches do chain (not under F5H_DIAG_SKIP_LN, not while a chained class is probed): what
+  // backbone_part needs beside its part being the whole packed batch
+  int32_t chain_eligible;
+  int32_t lnfold;   // the call runs a norm fold (engine switch and shape; never beside the chain): prologue, graph key
+  int32_t fold_on;  // DiT: the LayerNorm fold's producers and consumers run
+  int32_t rms_on;   // UNetT: the RMSNorm fold's producers and consumers run
+  int32_t out_live_skip;  // an out-projection that updates in place skips its row tiles of padding only (live_len)
+  int32_t pad_skip, probe_class;  // the engine's switches as they stood at the start of the call
+};
+StepModes step_modes(const ModeIn& in);
+// The process-wide switches of the environment, read once: F5H_RES32=1 (fp32 residual on the 16-bit DiT path, A/B),
+// F5H_DIAG_SKIP_LN=1 (StepModes::do_ln), F5H_CHAIN_ZERO=memset (the chain's counters zeroed by a memset node, A/B)
+struct ProcSwitches {
+  bool res32, skip_ln, chain_zero_memset;
+};
+const ProcSwitches& proc_switches();
+
 // ---------------------------------------------------------------- one call
 struct Ctx {
   f5h_engine* e;
@@ -295,10 +342,8 @@ struct Ctx {
   int drop_audio, drop_text;  // single-branch forward only (f5h_forward with cfg_infer = 0)
   hipStream_t st2;            // second stream for the unconditional branch (step-graph capture), or null
   int site;  // probe launch-site counter, reset at the start of every step's enqueue
-  int chain;  // this call may run the phase chain (engine switch, shape, and chain_admit's per-device check)
-  int lnfold;  // this call runs the LayerNorm fold (engine switch, shape; never beside the chain)
-  int store;   // the engine's store policy at the start of the call
-  int mx8;     // the engine's MX8 class mask at the start of the call (0: not an F5H_MXFP8 engine)
+  StepModes m;  // the call's modes (step_modes, with chain_admit's answer applied): chain, folds, MX8 classes, ...
+  int store;    // the engine's store policy at the start of the call
   double* hp;  // host milliseconds of the call by phase (kHostPhases, f5h_last_call_host_ms), or null
   // ragged sampling (f5h_sample_ragged; rag_B = 0 otherwise): rag_B utterances of at most rag_L frames as packed rows.
   // The row-local launches see B = 1, N = L = R (one "sequence" per CFG branch); the four kernels that reach across
@@ -332,7 +377,7 @@ struct ChainTicket {
   bool held = false;
   ~ChainTicket();
 };
-int chain_for_call(f5h_engine* e, const Ctx& c, ChainTicket& t);
+bool chain_for_call(f5h_engine* e, const Ctx& c, ChainTicket& t);
 int chain_fault_check(f5h_engine* e, hipStream_t st);
 int chain_fault_note(f5h_engine* e, hipStream_t st);
 // engine.cpp

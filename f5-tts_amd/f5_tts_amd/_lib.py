@@ -102,6 +102,7 @@ EXPORTS = (
     "f5h_attn_force_safe",
     "f5h_debug_tile_live",
     "f5h_debug_magic_div_sweep",
+    "f5h_debug_step_modes",
     "f5h_vocos_create",
     "f5h_vocos_destroy",
     "f5h_vocos_workspace_size",
@@ -376,6 +377,9 @@ def lib():
         L.f5h_debug_magic_div_sweep.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                 ctypes.POINTER(ctypes.c_uint32)]
         L.f5h_debug_magic_div_sweep.restype = ctypes.c_int64
+    if hasattr(L, "f5h_debug_step_modes"):  # absent from an older build (F5H_LIB)
+        L.f5h_debug_step_modes.argtypes = [ctypes.POINTER(i32), i32, ctypes.POINTER(i32), i32]
+        L.f5h_debug_step_modes.restype = ctypes.c_int
     L.f5h_vocos_create.argtypes = [ctypes.POINTER(VocosArch), ctypes.POINTER(Weight), i32, i32, ctypes.POINTER(vp)]
     L.f5h_vocos_create.restype = ctypes.c_int
     L.f5h_vocos_destroy.argtypes = [vp]

@@ -708,6 +708,17 @@ int f5h_debug_tile_live(const int32_t* live_len, int32_t live_seq, int32_t M, in
  * returns the count (0: exact over the whole range), or -1 for a bad range. limits (or null): receives the ranges
  * the launchers allow, {largest numerator + 1, largest divisor}. */
 int64_t f5h_debug_magic_div_sweep(uint32_t n_end, uint32_t d_lo, uint32_t d_hi, uint32_t* limits);
+/* Test hook (host only, no device, no engine, and the environment is not read): the engine's decision which modes a
+ * call runs in (the phase chain, the norm folds, the MXFP8 classes, the residual dtype, the pad-row skip, the two CFG
+ * chains), as every sample / forward call takes it once at its start. in[21]: backbone, dim, qk_norm,
+ * long_skip_connection, compute (f5h_compute; MXFP8 engines pass BF16), LayerNorm fold supported, RMSNorm fold
+ * supported, chain fault word present, MXFP8 engine, then the switches chain, ln_fold, pad_skip, graph_mode,
+ * cfg_streams (0 / 1 / 2), mx8 class mask, probed class (-1: none), then F5H_RES32, F5H_DIAG_SKIP_LN, then the call's
+ * use_cfg, batch mask, ragged. out[12]: mx8 classes in use, 16-bit residual, LayerNorms run, two CFG chains, the call
+ * may chain (before the per-device admission), its launches chain, a norm fold runs (call level), LayerNorm fold on,
+ * RMSNorm fold on, the in-place out-projection skips pad-row tiles, and pad_skip and the probed class as given.
+ * Returns F5H_EINVAL unless n_in == 21 and n_out == 12. */
+int f5h_debug_step_modes(const int32_t* in, int32_t n_in, int32_t* out, int32_t n_out);
 
 /* ---------------------------------------------------------------------------------------
  * Vocos decoder (mel -> waveform), SURVEY §8(f1): the step after the CFM path, replacing
